@@ -44,7 +44,7 @@ extern "C" {
 #pragma GCC visibility push(default)   /* the library is built with -fvisibility=hidden: these are its only exports */
 #endif
 
-#define VS_ABI_VERSION 9
+#define VS_ABI_VERSION 10
 
 /* activation codes */
 #define VS_ACT_RELU 0     /* VoiceFilter conv stack (models/voicefilter/model.py:21..54), head */
@@ -612,6 +612,24 @@ int vs_wav_to_spec(const vs_loss_dims* dims, const float* wav, float* spec, floa
  * (utils/audio_processor.py:478-491; est_mask*mixed_spec from utils/generic_utils.py:496).  mask may be NULL. */
 int vs_spec_to_wav(const vs_loss_dims* dims, const float* spec, const float* mask, const float* phase, float* wav,
                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* =============================================================================================
+ * Evaluation metric: single-source BSS-eval SDR, the number the reference reports for every test item
+ * (utils/generic_utils.py:476-530: mir_eval.separation.bss_eval_sources(clean_wav, est_wav, False)[0][0];
+ * test.py "Mean Test SDR", test_all_checkpoints.py's best-checkpoint choice).  Per row, with the fixed
+ * 512-tap distortion filter: C = G^-1 D (G: Toeplitz autocorrelation of the reference, lags 0..511;
+ * D: reference x estimate cross-correlation), P = ref * C (N + 511 samples),
+ * SDR = 10 log10(sum P^2 / sum ([est, 0] - P)^2), +inf when the denominator is 0.  fp64 throughout, sums in
+ * an order fixed by N alone: bitwise reproducible, and a row's value does not depend on B.
+ * ============================================================================================= */
+/* bytes of workspace vs_sdr needs for B rows of N samples; 0 for B <= 0, N <= 0 or sizes beyond the limits of vs_sdr */
+size_t vs_sdr_workspace_bytes(int B, long long N);
+/* ref, est: [B][N] fp32 (1 <= B <= 2^20, 1 <= N <= 2^40); sdr: [B] doubles (dB); status: [B] ints, 0 = ok,
+ * 1 = the reference or the estimate row is all zero (mir_eval raises ValueError), 2 = the Toeplitz solve failed
+ * (a prediction error <= 0 or not finite); a row with status != 0 gets NaN.  ws: vs_sdr_workspace_bytes(B, N)
+ * bytes, 256-byte aligned.  Five launches on `stream`, no synchronisation. */
+int vs_sdr(const float* ref, const float* est, int B, long long N, double* sdr, int* status,
+           void* workspace, size_t workspace_bytes, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -19,7 +19,7 @@ PROF_NAMES = ("cnn1", "cnn2", "cnn3", "cnn4", "cnn5", "cnn6", "cnn7", "cnn8", "l
               "fwd_bn", "bwd_head", "bwd_lstm_rec", "bwd_lstm_gemm", "bwd_bn",
               "wgrad_cnn2", "wgrad_cnn3", "wgrad_cnn4", "wgrad_cnn5", "wgrad_cnn6", "wgrad_cnn7",
               "dgrad_cnn2", "dgrad_cnn3", "dgrad_cnn4", "dgrad_cnn5", "dgrad_cnn6", "dgrad_cnn7", "bwd_edge")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class VsDims(Structure):
@@ -191,6 +191,9 @@ SIGNATURES = {
     "vs_spec_to_wav": (c_int, [POINTER(VsLossDims), _P, _P, _P, _P, _P, c_size_t, _P]),
     "vs_sigmoid_bwd": (c_int, [_P, _P, _P, c_longlong, _P]),
     "vs_colsum": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    # evaluation metric
+    "vs_sdr_workspace_bytes": (c_size_t, [c_int, c_longlong]),
+    "vs_sdr": (c_int, [_P, _P, c_int, c_longlong, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -1,0 +1,138 @@
+"""Checkpoint evaluation on the GPU: the reference's test.py and test_all_checkpoints.py.
+
+    python -m voicesplit_amd.evaluate -c config.json -d TEST_DIR --checkpoint_path checkpoint_1000.pt
+        Mean Test Loss: ...
+        Mean Test SDR: ...
+    python -m voicesplit_amd.evaluate -c config.json -d TEST_DIR --checkpoints_path LOG_DIR [--json FILE]
+        every *.pt of LOG_DIR but best_checkpoint.pt, in sorted order; prints the best checkpoint by SDR and by loss,
+        copies the best by SDR to LOG_DIR/best_checkpoint.pt and writes the per-checkpoint table as JSON
+        (default LOG_DIR/sdr_loss_per_checkpoint.json; the reference writes a .np array)
+
+Items are read as the reference's evaluation dataset reads them (utils/dataset.py:43-56): the embedding (``*-emb.pt``),
+the target and mixed waveforms (``c.dataset['format']``); the mixture's spectrogram and phase and the target spectrogram
+come from the GPU front end (``audio.wav_to_spec``), the estimate from ``audio.spec_to_wav`` and the SDR from
+``metrics.bss_sdr`` -- the whole of ``validation(test=True)`` (utils/generic_utils.py:476-530) on the device, in batches of
+``c.test_config['batch_size']`` items (which must share a length).  Scores are ``Trainer.evaluate``'s.
+"""
+import argparse
+import json
+import os
+import shutil
+from glob import glob
+
+import torch
+
+from .trainer import Trainer, load_wav
+
+
+class EvalDataset:
+    """(emb, target_wav, mixed_wav, names) per item of ``test_dir``, sorted by the ``c.dataset['format']`` globs."""
+
+    def __init__(self, c, test_dir: str):
+        if not os.path.isdir(test_dir):
+            raise FileNotFoundError("Test or Train dataset dir is incorrect! Fix it in config.json: " + str(test_dir))
+        fmt = c.dataset["format"]
+        find = lambda g: sorted(glob(os.path.join(test_dir, g)))
+        self.emb, self.target_wav, self.mixed_wav = (find(fmt[k]) for k in ("emb", "target_wav", "mixed_wav"))
+        if not (len(self.emb) == len(self.target_wav) == len(self.mixed_wav)):
+            raise ValueError(" The number of target and mixed Specs and Embs not Match! Check its")
+        if not self.emb:
+            raise ValueError(f" Test files not found in {test_dir}!")
+        self.sr = int(c.audio[c.audio["backend"]]["sample_rate"])
+
+    def __len__(self):
+        return len(self.emb)
+
+    def __getitem__(self, i):
+        return (torch.load(self.emb[i]), load_wav(self.target_wav[i], self.sr), load_wav(self.mixed_wav[i], self.sr),
+                (self.emb[i], self.target_wav[i], self.mixed_wav[i]))
+
+
+def eval_batches(c, ds: EvalDataset, device):
+    """``Trainer.evaluate``'s batches: (emb, target_spec, mixed_spec, seq_len, target_wav (host), mixed_phase), in dataset
+    order, ``c.test_config['batch_size']`` items each; items whose embedding is [0] are dropped (utils/dataset.py:93-95)."""
+    from . import audio
+    acfg = c.audio[c.audio["backend"]]
+    bs = int(c["test_config"]["batch_size"]) if "test_config" in c else 1          # config.json:33-36 (1 when absent)
+    for lo in range(0, len(ds), bs):
+        items = [ds[i] for i in range(lo, min(lo + bs, len(ds)))]
+        items = [it for it in items if it[0].tolist() != [0]]
+        if not items:
+            continue
+        lengths = {(it[1].shape[0], it[2].shape[0]) for it in items}
+        if len(lengths) != 1 or items[0][1].shape[0] != items[0][2].shape[0]:
+            desc = ", ".join(f"{os.path.basename(it[3][1])} ({it[1].shape[0]}) / {os.path.basename(it[3][2])} ({it[2].shape[0]})"
+                             for it in items)
+            raise ValueError(f"items of one test batch must share a length (test_config.batch_size = {bs}): {desc}")
+        emb = torch.stack([it[0].float().reshape(-1) for it in items]).to(device)
+        target_wav = torch.stack([it[1] for it in items])
+        mixed_wav = torch.stack([it[2] for it in items]).to(device)
+        seq_len = torch.full((len(items),), mixed_wav.shape[1], dtype=torch.int32, device=device)
+        mixed, phase = audio.wav_to_spec(mixed_wav, acfg, want_phase=True)
+        target, _ = audio.wav_to_spec(target_wav.to(device), acfg, want_phase=False)
+        yield emb, target, mixed, seq_len, target_wav, phase
+
+
+def build_trainer(c, device) -> Trainer:
+    from . import VoiceFilter, VoiceSplit
+    if c.model_name == "voicefilter":
+        model = VoiceFilter(c)
+    elif c.model_name == "voicesplit":
+        model = VoiceSplit(c)
+    else:
+        raise Exception(" The model '" + c.model_name + "' is not suported")
+    return Trainer(model.to(device), c)
+
+
+def score_checkpoint(tr: Trainer, path: str, ds: EvalDataset, device):
+    """(mean_loss, mean_sdr) of one checkpoint (test.py:test + validation(test=True))."""
+    tr.load_checkpoint(path)
+    return tr.evaluate(eval_batches(tr.c, ds, device))
+
+
+def main(argv=None):
+    from . import load_config
+    ap = argparse.ArgumentParser(description="Mean test loss and SDR of VoiceSplit checkpoints (test.py / test_all_checkpoints.py)")
+    ap.add_argument("-c", "--config_path", required=True, help="json file with configurations")
+    ap.add_argument("-d", "--dataset_dir", default="./", help="directory of the test items")
+    which = ap.add_mutually_exclusive_group(required=True)
+    which.add_argument("--checkpoint_path", help="one checkpoint (test.py)")
+    which.add_argument("--checkpoints_path", help="a directory of checkpoints (test_all_checkpoints.py)")
+    ap.add_argument("--json", default=None, help="--checkpoints_path: where the per-checkpoint table goes")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("voicesplit_amd.evaluate needs a GPU: the evaluation path has no CPU implementation")
+    c = load_config(args.config_path)
+    c.dataset["test_dir"] = args.dataset_dir
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ds = EvalDataset(c, args.dataset_dir)
+    tr = build_trainer(c, dev)
+    if args.checkpoint_path:
+        mean_loss, mean_sdr = score_checkpoint(tr, args.checkpoint_path, ds, dev)
+        print("Mean Test Loss:", mean_loss)
+        print("Mean Test SDR:", mean_sdr)
+        return mean_loss, mean_sdr
+    paths = [p for p in sorted(glob(os.path.join(args.checkpoints_path, "*.pt"))) if os.path.basename(p) != "best_checkpoint.pt"]
+    if not paths:
+        raise FileNotFoundError(f"no *.pt checkpoints in {args.checkpoints_path}")
+    table = []
+    for p in paths:
+        mean_loss, mean_sdr = score_checkpoint(tr, p, ds, dev)
+        print(f"{p}: Mean Test Loss: {mean_loss} Mean Test SDR: {mean_sdr}", flush=True)
+        table.append({"checkpoint": p, "mean_sdr": mean_sdr, "mean_loss": mean_loss})
+    scored = [t for t in table if t["mean_sdr"] == t["mean_sdr"]]          # NaN: no item of the set could be scored
+    if not scored:
+        raise RuntimeError("no checkpoint has a mean SDR: every test item was skipped")
+    best_sdr = max(scored, key=lambda t: t["mean_sdr"])
+    best_loss = min(table, key=lambda t: t["mean_loss"])
+    print("Best SDR checkpoint is: ", best_sdr["checkpoint"], "Best Loss checkpoint is: ", best_loss["checkpoint"],
+          "Best SDR:", best_sdr["mean_sdr"], "Best Loss:", best_loss["mean_loss"])
+    shutil.copyfile(best_sdr["checkpoint"], os.path.join(args.checkpoints_path, "best_checkpoint.pt"))
+    out = args.json or os.path.join(args.checkpoints_path, "sdr_loss_per_checkpoint.json")
+    with open(out, "w") as f:
+        json.dump({"checkpoints": table, "best_sdr": best_sdr, "best_loss": best_loss}, f, indent=1)
+    return table
+
+
+if __name__ == "__main__":
+    main()

@@ -362,8 +362,7 @@ class Trainer:
     @torch.no_grad()
     def validate(self, batches: Iterable) -> float:
         """Mean criterion value over this rank's validation batches in eval mode, averaged over ranks
-        (the loss part of utils/generic_utils.py:476-530; its SDR column needs mir_eval and stays
-        with the reference's test.py)."""
+        (the loss part of utils/generic_utils.py:476-530; ``evaluate`` adds its SDR column)."""
         self.model.eval()
         tot, cnt = 0.0, 0
         for emb, target, mixed, seq_len, _tw, phase in batches:
@@ -381,6 +380,50 @@ class Trainer:
             dist.all_reduce(acc, group=self.group)
         self.model.train()
         return float(acc[0] / acc[1]) if acc[1] > 0 else float("nan")
+
+    @torch.no_grad()
+    def evaluate(self, batches: Iterable):
+        """(mean_loss, mean_sdr) over this rank's test batches, averaged over ranks: the ``test=True`` branch of
+        utils/generic_utils.py:476-530 (test.py's "Mean Test Loss" / "Mean Test SDR"), a batch at a time on the device:
+
+            mask = model(mixed, emb);  est_wav = ap.inv_spectrogram(mask * mixed, phase)     :495-504
+            sdr  = bss_eval_sources(target_wav, est_wav, False)[0][0]                         :510
+
+        mean_loss is computed exactly as ``validate`` computes it (equal to ``validate(batches)``); mean_sdr is the mean
+        over the rows whose SDR exists (``metrics.bss_sdr`` status 0): a silent reference or estimate is skipped, as the
+        reference's ``except: continue`` skips it.  Batches are ``validate``'s tuples; the 5th element (target_wav) must be
+        the [B, S] target waveform, S = hop * (T - 1)."""
+        from . import audio, metrics
+        self.model.eval()
+        acfg = self.c.audio[self.c.audio["backend"]]
+        tot, cnt = 0.0, 0
+        dev = self.device
+        sdr_acc = torch.zeros(2, dtype=torch.float64, device=dev)          # (sum of SDRs, rows scored), on the device
+        for emb, target, mixed, seq_len, target_wav, phase in batches:
+            if emb is None or len(emb) == 0:                                # as validate: nothing left of this batch
+                continue
+            if target_wav is None:
+                raise ValueError("evaluate needs the target waveform (5th element of the batch)")
+            emb, target, mixed, phase = (t.to(dev) for t in (emb, target, mixed, phase))
+            if seq_len is not None:
+                seq_len = seq_len.to(dev).reshape(-1)
+            mask = self.model(mixed, emb)                                   # :495
+            tot += float(self.criterion(mask, mixed, target, seq_len, phase).item())
+            cnt += 1
+            est_wav = audio.spec_to_wav(mixed, phase, acfg, mask=mask)      # :496-504
+            sdr, status = metrics.bss_sdr(target_wav.to(dev, torch.float32), est_wav)
+            ok = status == 0
+            sdr_acc += torch.stack([torch.where(ok, sdr, torch.zeros_like(sdr)).sum(), ok.sum().to(torch.float64)])
+        acc = torch.tensor([tot, float(cnt)], dtype=torch.float64, device=dev)
+        acc = torch.cat([acc, sdr_acc.to(dev)])
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(acc, group=self.group)
+        self.model.train()
+        acc = acc.tolist()
+        mean_loss = acc[0] / acc[1] if acc[1] > 0 else float("nan")
+        mean_sdr = acc[2] / acc[3] if acc[3] > 0 else float("nan")
+        return mean_loss, mean_sdr
 
     def _with_decisions(self, batches: Iterable):
         """Yields (batch, have, next_missing) for ``train_step``.  One rank: have = None (decided in the step, no collective).
