@@ -433,7 +433,13 @@ int vs_forward_train(const vs_dims* dims, const vs_params* params, const float* 
  * tensor vs_forward_train returned; conv_act / bn_mode / dims / params must be those of the forward
  * call and the parameters unchanged since (VS_MATH_BF16: the tape already holds this pass's weight
  * images -- conv_packed_t, lstm_packed_t, the bf16 W_ih -- written by vs_forward_train).  The
- * gradient wrt the spectrogram x is not produced (the reference never asks for it: x is data). */
+ * gradient wrt the spectrogram x is not produced (the reference never asks for it: x is data).
+ * Constraint on the caller, not checked here: every weight, and under VS_BN_EVAL the BatchNorm
+ * running statistics, must hold the values they had in the vs_forward_train call that filled this
+ * tape.  Some are read live here and some from the tape's images, so an edit in between (optimizer
+ * step, a VS_BN_TRAIN forward moving the running statistics) silently mixes old and new values
+ * (voicesplit_amd/model.py puts them under torch's saved-tensor version check).  Several
+ * tapes may be in flight; each backward needs only its own. */
 int vs_backward(const vs_dims* dims, const vs_params* params, const float* x, const float* dvec,
                 int conv_act, int bn_mode, void* tape, size_t tape_bytes,
                 const float* mask, const float* dmask, const vs_grads* grads, void* stream);

@@ -58,16 +58,25 @@ class _MaskForward(torch.autograd.Function):
         module.__dict__["_last_tape"] = (weakref.ref(tape), dims)
         ctx.training = module.training
         ctx.names = [n for n, _ in module._named_params()]
-        ctx.save_for_backward(x, dvec_c, mask)
+        # vs_backward reads some weights live and others from images the tape took of them here, next to activations the
+        # weights of this call produced.  Saving every parameter (and, behind an eval-mode BatchNorm forward, the running
+        # statistics, as torch's batch_norm saves them) puts them under torch's version check: an in-place edit between forward
+        # and backward (optimizer step, load_state_dict, a train-mode forward moving the running statistics) raises instead of
+        # mixing old and new weights.  The versions are taken behind _bump_bn_counters above.  No copies: the saved tensors are
+        # the module's own.
+        ctx.buffer_names = [] if module.training else [k for k in sd if k.endswith(("running_mean", "running_var"))]
+        ctx.save_for_backward(x, dvec_c, mask, *params, *(sd[k] for k in ctx.buffer_names))
         return mask
 
     @staticmethod
     def backward(ctx, grad_mask):
-        x, dvec, mask = ctx.saved_tensors
+        x, dvec, mask, *saved = ctx.saved_tensors
         module = ctx.module
         if ctx.tape is None:
             raise RuntimeError("voicesplit_amd: backward called twice on the same forward (the tape was released)")
         sd = module._tensors()
+        # the tensors the forward ran on and the version check vouched for, also when a parameter was re-assigned since
+        sd.update(zip(ctx.names + ctx.buffer_names, saved))
         sink = module.__dict__.get("_grad_sink")
         grads = ops.backward(sd, x, dvec, ctx.dims, module.conv_act, ctx.training, ctx.tape, mask,
                              grad_mask.contiguous(), want_dvec=ctx.needs_input_grad[2], sink=sink,
