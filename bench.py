@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the hot path on MI355X: utterances/s of the VoiceSplit mask-prediction path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--mode train|forward|longform] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--mode train|forward|longform] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json metric "utterances/sec (3 s clips, B=64) fwd+bwd"): B=64 synthetic
 [64,301,601] spectrograms + 256-d d-vectors per GPU, random-init weights of the reference
@@ -24,12 +24,17 @@ reference, tests/test_gpu_bf16.py) -- plus
   roofline     -- the dominant kernel (5x5 64->64 conv: cnn3..cnn7 forward and their data gradients, 10 launches
                   per training step): algorithmic FLOPs per launch / mean launch time from HIP events recorded
                   inside the timed region; the weight-gradient kernel and the LSTM input GEMM next to it
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full also runs, after the timed
+steps and the dump, everything that takes runs of its own (--no-extras / --no-cpu-baseline drop parts of it):
   forward      -- BASELINE configs[1] timed in the same process: forward only in the fp32-class arithmetic (fp32 results
                   from split-f16 MFMAs, <= 1e-4 relative vs the reference); forward_bf16: the same in bf16
   fp32_class   -- the same training step in the fp32-class arithmetic (the headline of rounds 1-2), own roofline figures
   fp32_strict  -- the same step on the fp32 matrix cores (bitwise an fmaf chain), 3 steps
   longform     -- BASELINE configs[4] as a short sub-leg (51 clips of 30 s = 510 windows per step, 256 windows per forward batch),
                   in bf16 and in the fp32-class arithmetic (`--mode longform` is the full line of that configuration)
+  eval_latency -- one eval-mode forward at the reference's own evaluation batch sizes, B=1 and B=5
+  rccl         -- N = 1: the gradient bucket through a one-rank ncclAllReduce; N > 1: the ranks' buckets compared
+  box_calibration -- one fixed bf16 GEMM launch that says how fast this box's clock runs
   cpu_baseline -- the oracle (torch CPU restatement of the reference) timed on the host cores, B=1 and B=4; in training mode
                   forward + autograd backward from a STAND-IN loss (a fixed d(loss)/d(mask)).
 --conv-math f16x3 makes the fp32-class step the line and bf16 the sub-object.
@@ -237,7 +242,7 @@ def self_launch(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -250,8 +255,8 @@ def main():
                     help="arithmetic / layout of the conv stack and the LSTM GEMMs (default: the library default, f16x3)")
     ap.add_argument("--loss", default="sisnr", choices=["sisnr", "powerlaw", "fixed"],
                     help="training mode: the reference's SI-SNR loss through the GPU iSTFT (default), or a fixed upstream gradient")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward / bf16 / fp32_strict sub-objects of the training line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the forward / bf16 / fp32_strict sub-objects of the training line")
     ap.add_argument("--force-collectives", action="store_true",
                     help="train mode at --gpus 1: run the N > 1 code path of the step (bucket all-reduces over a one-rank RCCL group, "
                          "loss through the host ring, skip flag in the bucket) -- what one GPU can measure of it")
@@ -271,9 +276,17 @@ def main():
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy: training mode the loss it returned, every parameter "
                          "gradient (grads) and the floating-point state_dict entries after the update (state), each flattened in state_dict order; forward / "
                          "longform mode the mask.  At most 64 MB in all: a larger array becomes a fixed seeded sample of its elements")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and the dump), also run what takes runs of its own: the training line's sub-legs, the RCCL "
+                         "leg, the box calibration and the CPU baseline.  Without it a run does only what the headline figure needs")
+    args = ap.parse_args(argv)
     if args.batch is None:
         args.batch = 256 if args.mode == "longform" else 64
+    return args
+
+
+def main():
+    args = parse_args()
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
@@ -543,12 +556,19 @@ def main():
         comm = {"forced_collectives_on_one_rank": True, "split_allreduce": bool(trainer.split_allreduce), "loss_lag": trainer.loss_lag}
         if split_choice:
             comm["split_allreduce_calibration"] = split_choice
-    # ---- RCCL leg (outside the timed region) ---------------------------------------------------------
+    # ---- RCCL leg (--full, outside the timed region) ------------------------------------------------
     # N > 1: every rank must hold the same bucket after the step's all-reduce (a checksum per rank, gathered).
     # N = 1: the step's exchange is a no-op, so the device collective is exercised once on its own: a
     # one-rank process group, the 75.5 MB bucket through ncclAllReduce, timed with HIP events.
     rccl = None
-    if train:
+    if train and not args.full:
+        # a plain run reports only what the timed steps' own collectives recorded (N > 1, --force-collectives)
+        if comm:
+            rccl = dict({"rccl_ranks": world}, **comm)
+        if forced:
+            import torch.distributed as tdist
+            tdist.destroy_process_group()
+    elif train:
         try:
             import torch.distributed as tdist
             if world > 1:
@@ -589,7 +609,7 @@ def main():
     # outside the region says which kind of box this line comes from -- the bf16 LSTM input contraction at the metric shape
     # (19264 x 3200 x 4808, the same seeded random operands everywhere: the clock of these kernels follows the operands' toggle rate).
     box = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             M_, N_, K_ = 19264, 3200, 4808
             Kp_ = (K_ + 63) // 64 * 64
@@ -835,7 +855,7 @@ def main():
     fwd = fwd16 = other = strict = lform = lat = None
     if not train:
         feed_info = None
-    if train and not args.no_extras:
+    if train and args.full and not args.no_extras:
         fwd = forward_leg(model, "f16x3" if conv_math == "bf16" else conv_math)      # configs[1]: fp32-class forward
         if conv_math == "bf16":
             fwd16 = forward_leg(model, "bf16")
@@ -939,7 +959,7 @@ def main():
             line["box_calibration"] = box
         if dumped is not None:
             line["outputs_dumped"] = dumped
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline("train" if train else "forward")
     if dist:
         dist.destroy_process_group()

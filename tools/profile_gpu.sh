@@ -13,11 +13,11 @@ export TMPDIR=/tmp
 (cd "$REPO/voicesplit_amd/csrc" && sha256sum *.hip *.h *.inc) > "$OUT/sources.sha256"
 # (ten steps: the first launch of a kernel in a process runs up to 2x long -- cold instruction cache, first touch of its operands -- and
 # weighed 1/20 in the four-step tables of rounds 2-5; 1/50 now)
-BENCH="python $REPO/bench.py --steps 9 --warmup 1 --no-cpu-baseline --no-extras $*"
+BENCH="python $REPO/bench.py --full --steps 9 --warmup 1 --no-cpu-baseline --no-extras $*"
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -f csv -- $BENCH > "$OUT/trace.log" 2>&1
 echo "trace rc=$?"
-ONE="python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras $*"
+ONE="python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras $*"
 KREG="conv64_mfma|conv64_wgrad|conv64_f16|gemm_f16x3|gemm_pre|gemm_bf16|lstm16|lstm_persistent|lstm_bwd_persistent|nhwc_conv_kernel|nhwc_conv_f16x3|nhwc_wgrad"
 timeout 600 rocprofv3 --kernel-trace --kernel-include-regex "$KREG" --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d "$OUT/pmc_sq" -o pmc -f csv -- $ONE > "$OUT/pmc_sq.log" 2>&1
 echo "pmc_sq rc=$?"
