@@ -29,6 +29,8 @@ constexpr float kLn10Over20 = 0.11512925464970229f;
 
 struct LossShape {
   int B, T, F, n_fft, hop, win, S;   // S = hop*(T-1) samples per utterance
+  int lead;                          // window sample j of frame t is output sample hop*t - lead + j: n_fft/2 - (n_fft-win)/2
+                                     // (the window sits at (n_fft-win)/2 in the frame: win/2 only for even win)
   int K, ldk;                        // K = 2F (re | im), ldk = K rounded up to 4
   float min_level_db, ref_level_db;
   int periodic;      // 0: hann(win, periodic=False) (torch_spec2wav :509); 1: librosa/scipy 'hann' (fftbins=True)
@@ -75,7 +77,7 @@ __global__ void istft_basis_kernel(float* __restrict__ basis, LossShape s, float
 __global__ void istft_envelope_kernel(float* __restrict__ env, LossShape s) {
   const int sp = blockIdx.x * blockDim.x + threadIdx.x;
   if (sp >= s.S) return;
-  const int off = s.win / 2;                 // sample sp sits at frame-local j = sp - hop*t + off
+  const int off = s.lead;                    // sample sp sits at frame-local j = sp - hop*t + off
   float e = 0.f;
   int t_hi = (sp + off) / s.hop;
   if (t_hi > s.T - 1) t_hi = s.T - 1;
@@ -113,7 +115,7 @@ void spec_to_reim_kernel(const float* __restrict__ a, const float* __restrict__ 
 }
 
 // ---- analysis side: wav -> frames -> (re | im) -> normalised dB magnitude + phase ---------------
-// frames[m][j] = w[j] * wav_reflect[b][hop*t - win/2 + j]     (librosa.stft: center=True, reflect padding;
+// frames[m][j] = w[j] * wav_reflect[b][hop*t - lead + j]     (librosa.stft: center=True, reflect padding;
 // only the win samples under the centred window matter)
 __global__ __launch_bounds__(256)
 void stft_frames_kernel(const float* __restrict__ wav, float* __restrict__ frames, LossShape s, unsigned* __restrict__ amax = nullptr) {
@@ -123,7 +125,7 @@ void stft_frames_kernel(const float* __restrict__ wav, float* __restrict__ frame
     const long long m = i / s.win;
     const int j = (int)(i - m * s.win);
     const int b = (int)(m / s.T), t = (int)(m - (long long)b * s.T);
-    int idx = s.hop * t - s.win / 2 + j;
+    int idx = s.hop * t - s.lead + j;
     if (idx < 0) idx = -idx;
     if (idx >= s.S) idx = 2 * (s.S - 1) - idx;
     const float v = hann_w(j, s) * wav[(size_t)b * s.S + idx];
@@ -163,13 +165,13 @@ void reim_to_features_kernel(const float* __restrict__ reim, float* __restrict__
   }
 }
 
-// wav[b][sp] = (sum_t frames[b*T+t][sp - hop*t + win/2]) / env[sp]
+// wav[b][sp] = (sum_t frames[b*T+t][sp - hop*t + lead]) / env[sp]
 __global__ __launch_bounds__(256)
 void overlap_add_kernel(const float* __restrict__ frames, const float* __restrict__ env, float* __restrict__ wav, LossShape s) {
   const int sp = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (sp >= s.S) return;
-  const int off = s.win / 2;
+  const int off = s.lead;
   int t_hi = (sp + off) / s.hop;
   if (t_hi > s.T - 1) t_hi = s.T - 1;
   float acc = 0.f;
@@ -181,7 +183,7 @@ void overlap_add_kernel(const float* __restrict__ frames, const float* __restric
   wav[(size_t)b * s.S + sp] = acc / env[sp];
 }
 
-// dframes[m][j] = dwav[b][sp] / env[sp],  sp = hop*t - win/2 + j  (0 outside the kept samples)
+// dframes[m][j] = dwav[b][sp] / env[sp],  sp = hop*t - lead + j  (0 outside the kept samples)
 __global__ __launch_bounds__(256)
 void overlap_add_bwd_kernel(const float* __restrict__ dwav, const float* __restrict__ env, float* __restrict__ dframes, LossShape s,
                             unsigned* __restrict__ amax = nullptr) {
@@ -191,7 +193,7 @@ void overlap_add_bwd_kernel(const float* __restrict__ dwav, const float* __restr
     const long long m = i / s.win;
     const int j = (int)(i - m * s.win);
     const int b = (int)(m / s.T), t = (int)(m - (long long)b * s.T);
-    const int sp = s.hop * t - s.win / 2 + j;
+    const int sp = s.hop * t - s.lead + j;
     const float v = (sp >= 0 && sp < s.S) ? dwav[(size_t)b * s.S + sp] / env[sp] : 0.f;
     dframes[i] = v;
     mx = fmaxf(mx, fabsf(v));
@@ -368,6 +370,7 @@ int make_shape(const vs_loss_dims* d, LossShape* s) {
   VS_REQUIRE(d->B <= 65535, "loss: B too large");
   s->B = d->B; s->T = d->T; s->F = d->F; s->n_fft = d->n_fft; s->hop = d->hop; s->win = d->win;
   s->S = d->hop * (d->T - 1);
+  s->lead = d->n_fft / 2 - (d->n_fft - d->win) / 2;
   s->K = 2 * d->F;
   s->ldk = (s->K + 3) & ~3;
   s->min_level_db = d->min_level_db; s->ref_level_db = d->ref_level_db;
@@ -388,7 +391,7 @@ int check_envelope(const LossShape& s) {
   bool hit = true;
   for (int i = 0; i < 5; ++i) hit = hit && key[i] == c_key[i];
   if (!hit) {
-    const int off = s.win / 2, den = s.periodic ? s.win : s.win - 1;
+    const int off = s.lead, den = s.periodic ? s.win : s.win - 1;
     auto env_at = [&](int sp) {
       double e = 0.0;
       int t_hi = (sp + off) / s.hop;
