@@ -44,7 +44,7 @@ extern "C" {
 #pragma GCC visibility push(default)   /* the library is built with -fvisibility=hidden: these are its only exports */
 #endif
 
-#define VS_ABI_VERSION 10
+#define VS_ABI_VERSION 11
 
 /* activation codes */
 #define VS_ACT_RELU 0     /* VoiceFilter conv stack (models/voicefilter/model.py:21..54), head */
@@ -636,6 +636,62 @@ size_t vs_sdr_workspace_bytes(int B, long long N);
  * bytes, 256-byte aligned.  Five launches on `stream`, no synchronisation. */
 int vs_sdr(const float* ref, const float* est, int B, long long N, double* sdr, int* status,
            void* workspace, size_t workspace_bytes, void* stream);
+
+/* =============================================================================================
+ * ABI 11.  The GE2E speaker encoder, inference only: reference audio -> the d-vector `dvec` that vs_forward* take
+ * (notebooks/GE2E-Seungwonpark-ExtractSpeakerEmbedding-...py with ap.get_mel, utils/audio_processor.py:460-467, in front):
+ *   mel  = log10(mel_basis @ |stft(wav)|^2 + 1e-6)                                               [n_mels][T], T = 1 + n / hop
+ *   x    = nn.LSTM(n_mels -> hidden, layers)(mel.unfold(1, window, stride))[:, -1, :]            [N][hidden]
+ *   proj = x @ proj_w^T + proj_b                                                                  [N][emb]
+ *   dvec = mean over the utterance's windows of proj / |proj|_2                                   [emb]
+ * nn.LSTM semantics: gate order i, f, g, o; bias b_ih + b_hh; zero initial state per window; layer l+1 reads layer l's h.
+ * The encoder is frozen (the reference never trains it): there is no backward pass.
+ * ============================================================================================= */
+typedef struct vs_speaker_dims {
+  int n_mels;   /* 40                                                                  */
+  int hidden;   /* 768; must be a multiple of 8                                        */
+  int layers;   /* 3; 1 .. 4                                                           */
+  int emb;      /* 256                                                                 */
+  int window;   /* 80 mel frames per window                                            */
+  int stride;   /* 40                                                                  */
+  int math;     /* VS_MATH_F16X3 (split-f16 products, fp32 accumulate) or VS_MATH_FP32 (plain fp32 FMA: the cross-check arm);
+                   VS_MATH_BF16 is refused with an error (no single-product arm is built) */
+} vs_speaker_dims;
+
+typedef struct vs_speaker_params {
+  const float* w_ih[4];       /* lstm.weight_ih_l{k}  [4 hidden][n_mels] (k = 0), [4 hidden][hidden] (k > 0) */
+  const float* w_hh[4];       /* lstm.weight_hh_l{k}  [4 hidden][hidden]                                     */
+  const float* b_ih[4];       /* lstm.bias_ih_l{k}    [4 hidden]                                             */
+  const float* b_hh[4];       /* lstm.bias_hh_l{k}    [4 hidden]                                             */
+  const float* proj_w;        /* proj.linear_layer.weight [emb][hidden]                                      */
+  const float* proj_b;        /* proj.linear_layer.bias   [emb]                                              */
+} vs_speaker_params;
+
+/* Weights packed once (vs_prepare_weights' counterpart): fp32 copies of what the small launches read, and per layer
+ * [W_ih | W_hh] as split-f16 planes in matrix-core fragment order with their power-of-two scale (VS_MATH_F16X3) or as fp32 rows
+ * (VS_MATH_FP32).  vs_speaker_prepared_bytes depends on the dims alone (0 + vs_last_error for bad dims); the buffer is 256-byte
+ * aligned; the caller re-prepares when a parameter or dims.math changes.  vs_speaker_embed reads the prepared buffer only. */
+size_t vs_speaker_prepared_bytes(const vs_speaker_dims* dims);
+int vs_speaker_prepare(const vs_speaker_dims* dims, const vs_speaker_params* params, void* prepared, size_t prepared_bytes, void* stream);
+/* Workspace of vs_speaker_embed for N windows over total_frames mel frames (monotone in both, multiple of 256; 0 + vs_last_error for bad arguments). */
+size_t vs_speaker_workspace_bytes(const vs_speaker_dims* dims, int N, int total_frames);
+/* mel [n_mels][total_frames]: the log-mels of U utterances side by side along time.  utt_frames [U + 1] and utt_windows [U + 1]
+ * (device int32): utterance u owns frames [utt_frames[u], utt_frames[u+1]) and windows [utt_windows[u], utt_windows[u+1]) of the N;
+ * window n of utterance u covers frames utt_frames[u] + (n - utt_windows[u]) * stride + [0, window) -- the windows are gathered
+ * here, no unfolded copy exists.  An utterance may own no window (shorter than `window`): its d-vector is all zero.
+ * Outputs, each may be NULL: h_last [N][hidden] (last layer, last step), proj [N][emb] (un-normalised), dvec [U][emb].
+ * window + layers - 1 step launches on `stream`, one per tick of the layer wavefront; nothing persistent, no synchronisation.
+ * A window's h_last / proj do not depend on N or on its position in the batch (bitwise). */
+int vs_speaker_embed(const vs_speaker_dims* dims, const void* prepared, size_t prepared_bytes, const float* mel, int total_frames,
+                     const int* utt_frames, const int* utt_windows, int U, int N, float* h_last, float* proj, float* dvec,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* ap.get_mel for ONE clip of n samples, n > n_fft / 2 and otherwise any length (reflection at the clip's true end):
+ * wav [n] -> mel [n_mels][1 + n / hop] = log10(mel_basis @ |D|^2 + 1e-6), D = librosa.stft(n_fft, hop, win, hann, center, reflect).
+ * dims: n_fft, hop, win and F = n_fft / 2 + 1 are read (B, T and the dB levels are not).  mel_basis [n_mels][F]: the caller's
+ * (librosa.filters.mel).  The STFT is vs_wav_to_spec's split-f16 contraction. */
+size_t vs_logmel_workspace_bytes(const vs_loss_dims* dims, long long n, int n_mels);
+int vs_wav_to_logmel(const vs_loss_dims* dims, const float* wav, long long n, const float* mel_basis, int n_mels, float* mel,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

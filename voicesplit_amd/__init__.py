@@ -8,11 +8,15 @@ Public surface (mirrors the reference):
   reference's own module paths ``models.voicesplit.model`` / ``models.voicefilter.model``.
 * ``AttrDict`` / ``load_config``: the config object those constructors take
   (utils/generic_utils.py:560-573).
+* ``SpeakerEncoder`` / ``logmel`` / ``mel_filterbank``: the GE2E speaker encoder that turns reference audio into the
+  d-vector (notebooks/GE2E-Seungwonpark-ExtractSpeakerEmbedding-...py), ``voicesplit_amd/speaker.py``.
 * ``ops``: stage-level entry points over the C ABI of ``libvoicesplit_hip.so``.
 
 The compute path is the HIP library only; there is no PyTorch/CPU fallback.
 """
 from .config import AttrDict, load_config, default_config  # noqa: F401
 from .model import VoiceFilter, VoiceSplit  # noqa: F401
+from .speaker import SpeakerEncoder, logmel, mel_filterbank  # noqa: F401
 
-__all__ = ["VoiceSplit", "VoiceFilter", "AttrDict", "load_config", "default_config"]
+__all__ = ["VoiceSplit", "VoiceFilter", "AttrDict", "load_config", "default_config", "SpeakerEncoder", "logmel",
+           "mel_filterbank"]

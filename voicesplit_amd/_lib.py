@@ -19,7 +19,7 @@ PROF_NAMES = ("cnn1", "cnn2", "cnn3", "cnn4", "cnn5", "cnn6", "cnn7", "cnn8", "l
               "fwd_bn", "bwd_head", "bwd_lstm_rec", "bwd_lstm_gemm", "bwd_bn",
               "wgrad_cnn2", "wgrad_cnn3", "wgrad_cnn4", "wgrad_cnn5", "wgrad_cnn6", "wgrad_cnn7",
               "dgrad_cnn2", "dgrad_cnn3", "dgrad_cnn4", "dgrad_cnn5", "dgrad_cnn6", "dgrad_cnn7", "bwd_edge")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class VsDims(Structure):
@@ -52,6 +52,15 @@ class VsWsLayout(Structure):
 class VsLossDims(Structure):
     _fields_ = [("B", c_int), ("T", c_int), ("F", c_int), ("n_fft", c_int), ("hop", c_int), ("win", c_int),
                 ("min_level_db", c_float), ("ref_level_db", c_float)]
+
+
+class VsSpeakerDims(Structure):
+    _fields_ = [(n, c_int) for n in ("n_mels", "hidden", "layers", "emb", "window", "stride", "math")]
+
+
+class VsSpeakerParams(Structure):
+    _fields_ = [("w_ih", c_void_p * 4), ("w_hh", c_void_p * 4), ("b_ih", c_void_p * 4), ("b_hh", c_void_p * 4),
+                ("proj_w", c_void_p), ("proj_b", c_void_p)]
 
 
 class VsConvLayerGrad(Structure):
@@ -194,6 +203,13 @@ SIGNATURES = {
     # evaluation metric
     "vs_sdr_workspace_bytes": (c_size_t, [c_int, c_longlong]),
     "vs_sdr": (c_int, [_P, _P, c_int, c_longlong, _P, _P, _P, c_size_t, _P]),
+    # speaker encoder
+    "vs_speaker_prepared_bytes": (c_size_t, [POINTER(VsSpeakerDims)]),
+    "vs_speaker_prepare": (c_int, [POINTER(VsSpeakerDims), POINTER(VsSpeakerParams), _P, c_size_t, _P]),
+    "vs_speaker_workspace_bytes": (c_size_t, [POINTER(VsSpeakerDims), c_int, c_int]),
+    "vs_speaker_embed": (c_int, [POINTER(VsSpeakerDims), _P, c_size_t, _P, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "vs_logmel_workspace_bytes": (c_size_t, [POINTER(VsLossDims), c_longlong, c_int]),
+    "vs_wav_to_logmel": (c_int, [POINTER(VsLossDims), _P, c_longlong, _P, c_int, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -81,3 +81,17 @@ def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg) -> torch.T
     with torch.no_grad():
         mask = model(spec, dvec)
     return spec_to_wav(spec, phase, audio_cfg, mask=mask)
+
+
+def separate_with_reference(model, encoder, wav: torch.Tensor, ref_wavs, audio_cfg) -> torch.Tensor:
+    """``separate`` with the d-vectors computed here from reference audio of the wanted speakers: ref_wavs = one 1-D
+    waveform per row of wav (any length above n_fft / 2 samples and at least one encoder window of frames);
+    encoder = a ``speaker.SpeakerEncoder`` on the device."""
+    from .speaker import logmel
+    if len(ref_wavs) != wav.shape[0]:
+        raise ValueError(f"{len(ref_wavs)} reference waveforms for {wav.shape[0]} mixtures")
+    dvec, valid = encoder.embed_many([logmel(r, audio_cfg, encoder.num_mels) for r in ref_wavs])
+    if not bool(valid.all()):
+        short = [i for i, v in enumerate(valid.tolist()) if not v]
+        raise ValueError(f"reference waveforms {short} are shorter than one encoder window of {encoder.window} frames")
+    return separate(model, wav, dvec, audio_cfg)
