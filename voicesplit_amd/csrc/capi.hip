@@ -49,15 +49,6 @@ typedef VsProfScope ProfScope;
 
 namespace {
 
-constexpr float kBnEps = 1e-5f;       // nn.BatchNorm2d default (models/voicesplit/model.py:19)
-constexpr float kBnMomentum = 0.1f;
-
-// conv-stack table (models/voicesplit/model.py:15-52): KT, KF, time dilation
-struct Spec { int kt, kf, dil; };
-constexpr Spec kMid[6] = {{7, 1, 1}, {5, 5, 1}, {5, 5, 2}, {5, 5, 4}, {5, 5, 8}, {5, 5, 16}};
-
-inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-
 int check_dims(const vs_dims* d) {
   VS_REQUIRE(d != nullptr, "dims is NULL");
   VS_REQUIRE(d->B > 0 && d->T > 0 && d->F > 0 && d->E > 0 && d->H > 0 && d->FC1 > 0 && d->FC2 > 0,
@@ -102,9 +93,6 @@ int layout(const vs_dims* d, vs_ws_layout* L) {
   L->total_bytes = off;
   return 0;
 }
-
-template <typename T>
-inline T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
 int check_ws(const vs_dims* d, void* ws, size_t ws_bytes, vs_ws_layout* L) {
   if (int rc = layout(d, L)) return rc;
@@ -997,6 +985,100 @@ int vs_forward_prepared(const vs_dims* d, const vs_params* p, const void* prepar
   if (int rc = conv_stack_impl(d, p, x, conv_act, VS_BN_EVAL, ws, L, nullptr, (hipStream_t)stream, &P, &feat_rows)) return rc;
   if (int rc = bilstm_impl(d, p, nullptr, dvec, ws, L, nullptr, (hipStream_t)stream, &P, feat_rows)) return rc;
   return head_fwd_impl(d, p, nullptr, ws, ws_bytes, nullptr, mask, (hipStream_t)stream, P.head_packed);
+}
+
+// ---------------------------------------------------------------------------------------------
+// unit-test surface of the backward kernels (pass-through wrappers; the training schedule itself is train.hip)
+// ---------------------------------------------------------------------------------------------
+int vs_conv64_pack_dgrad(const float* w, float* packed, int KT, int KF, void* stream) {
+  return vs_conv64_pack_impl(w, packed, KT, KF, 1, (hipStream_t)stream);
+}
+
+int vs_conv64_wgrad(const float* dz, const float* in, float* partials, float* dw, int B, int T, int F, int KT, int KF,
+                    int dil, void* stream) {
+  VS_REQUIRE(dz && in && partials && dw, "conv64_wgrad: NULL argument");
+  return vs_conv64_wgrad_impl(dz, in, partials, dw, B, T, F, KT, KF, dil, (hipStream_t)stream);
+}
+
+int vs_conv64_wgrad_f16x3(const float* dz, const float* in, float* partials, float* dw, float* scratch8,
+                          int B, int T, int F, int KT, int KF, int dil, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VS_REQUIRE(dz && in && partials && dw && scratch8, "conv64_wgrad_f16x3: NULL argument");
+  unsigned* amax = reinterpret_cast<unsigned*>(scratch8 + 4);
+  if (int rc = vs_pow2_scale_impl(dz, (long long)B * 64 * T * F, amax, scratch8, stream)) return rc;
+  if (int rc = vs_pow2_scale_impl(in, (long long)B * 64 * T * F, amax + 1, scratch8 + 2, stream)) return rc;
+  return vs_conv64_wgrad_f16x3_impl(dz, in, scratch8, scratch8 + 2, partials, dw, B, T, F, KT, KF, dil, stream);
+}
+
+int vs_bn_act_bwd(const float* da, const float* z, float* dz, int C, long long R, int L, int act, int bn_mode,
+                  const float* scale, const float* shift, const float* mean, const float* invstd,
+                  float* dgamma, float* dbeta, float* dbias, double* stats, float* coef, void* stream) {
+  VS_REQUIRE(da && z && dz && scale && shift && mean && invstd && stats && coef, "bn_act_bwd: NULL argument");
+  return vs_bn_act_bwd_impl(da, z, dz, C, R, L, act, bn_mode == VS_BN_TRAIN, scale, shift, mean, invstd, dgamma, dbeta, dbias,
+                            stats, coef, nullptr, (hipStream_t)stream);
+}
+
+int vs_bn_act_bwd_first(const float* da, const float* z, const float* x, float* xpad, int B, int T, int F, int act, int bn_mode,
+                        const float* scale, const float* shift, const float* mean, const float* invstd,
+                        float* dgamma, float* dbeta, float* dbias, float* dw, double* stats, float* coef, double* acc, void* stream) {
+  VS_REQUIRE(da && z && x && xpad && scale && shift && mean && invstd && dw && stats && coef && acc, "bn_act_bwd_first: NULL argument");
+  return vs_bn_act_bwd_first_impl(da, z, x, xpad, B, T, F, act, bn_mode == VS_BN_TRAIN, scale, shift, mean, invstd, dgamma, dbeta, dbias,
+                                  dw, stats, coef, acc, (hipStream_t)stream);
+}
+
+int vs_conv_last_dgrad(const float* dz, const float* w, float* din, int B, int T, int F, void* stream) {
+  return vs_conv_last_dgrad_impl(dz, w, din, B, T, F, (hipStream_t)stream);
+}
+
+int vs_conv_last_wgrad(const float* dz, const float* in, float* partials, float* dw, int B, int T, int F, void* stream) {
+  return vs_conv_last_wgrad_impl(dz, in, partials, dw, B, T, F, (hipStream_t)stream);
+}
+
+int vs_conv_first_wgrad(const float* dz, const float* x, double* acc, float* dw, int B, int T, int F, void* stream) {
+  return vs_conv_first_wgrad_impl(dz, x, acc, dw, B, T, F, (hipStream_t)stream);
+}
+
+int vs_gemm(int layout_a, int layout_w, const float* A, int lda, const float* W, int ldw, float* C, int ldc,
+            int M, int N, int K, const float* bias, const float* gate, int ldg, int a_relu, int w_relu, int act,
+            int accumulate, int w_shift, int w_group, int splits, float* partials, void* stream) {
+  VS_REQUIRE(A && W && C, "gemm: NULL argument");
+  return vs_gemm_general_impl(layout_a, layout_w, A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, K, bias, nullptr, nullptr, 0, 1,
+                              gate, ldg, a_relu, w_relu, act, accumulate, w_shift, w_group, splits, partials, (hipStream_t)stream);
+}
+
+int vs_gemm_f16x3(int layout_a, int layout_w, const float* A, int lda, const float* W, int ldw, float* C, int ldc,
+                  int M, int N, int K, const float* bias, const float* gate, int ldg, int a_relu, int w_relu, int act,
+                  int accumulate, float* scratch8, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VS_REQUIRE(A && W && C && scratch8, "gemm_f16x3: NULL argument");
+  unsigned* amax = reinterpret_cast<unsigned*>(scratch8 + 4);
+  // the operands are dense [rows][ld] buffers here: scale over the whole buffers
+  if (int rc = vs_pow2_scale_impl(A, (long long)(layout_a ? K : M) * lda, amax, scratch8, stream)) return rc;
+  if (int rc = vs_pow2_scale_impl(W, (long long)(layout_w ? K : N) * ldw, amax + 1, scratch8 + 2, stream)) return rc;
+  return vs_gemm_f16x3_impl(layout_a, layout_w, A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, K, bias, nullptr, nullptr, 0, 1,
+                            gate, ldg, a_relu, w_relu, act, accumulate, scratch8, scratch8 + 2, stream);
+}
+
+int vs_bilstm_recurrent_train(const float* xg, const float* packed_whh, float* state, float* out, float* gates_save,
+                              float* c_save, int B, int T, int H, void* stream) {
+  return vs_bilstm_recurrent_impl(xg, packed_whh, state, out, gates_save, c_save, B, T, H, (hipStream_t)stream);
+}
+
+int vs_lstm_pack_t(const float* w_hh_fwd, const float* w_hh_bwd, float* packed_t, int H, void* stream) {
+  return vs_lstm_pack_t_impl(w_hh_fwd, w_hh_bwd, packed_t, H, (hipStream_t)stream);
+}
+
+int vs_bilstm_recurrent_bwd(const float* packed_t, float* state, float* gates, const float* c_all, const float* dout,
+                            int B, int T, int H, void* stream) {
+  return vs_bilstm_bwd_recurrent_impl(packed_t, state, gates, c_all, dout, B, T, H, (hipStream_t)stream);
+}
+
+int vs_sigmoid_bwd(const float* dmask, const float* mask, float* dlogits, long long n, void* stream) {
+  return vs_sigmoid_bwd_impl(dmask, mask, dlogits, n, (hipStream_t)stream);
+}
+
+int vs_colsum(const float* x, int ld, int groups, int rows, int N, float* out, int ldo, void* stream) {
+  return vs_colsum_impl(x, ld, groups, rows, N, out, ldo, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -310,8 +310,6 @@ void reim_to_dmask_kernel(const float* __restrict__ mixed, const float* __restri
   }
 }
 
-inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-
 struct LossLayout { size_t basis, fbasis, env, reim_e, reim_t, frames_e, frames_t, wav_e, wav_t, dwav, mom, coef, amax, scales, total; };
 
 // ---- PowerLaw_Compressed_Loss (utils/generic_utils.py:353-373), the criterion train.py:74-75 picks
@@ -439,9 +437,6 @@ void make_layout(const LossShape& s, LossLayout* L) {
   L->scales = take(4 * 2 * 4);                        // {s, 1/s}: reim (estimate), reim (target), d(frames), basis
   L->total = off;
 }
-
-template <typename T>
-inline T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
 }  // namespace
 

@@ -32,12 +32,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 constexpr int kMaxLayers = 4;
 constexpr float kHScale = 1024.f;      // h is exchanged as f16(h * 2^10) + f16(remainder), as in lstm.hip
 
-inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-template <typename T>
-inline T* at(void* p, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(p) + off); }
-template <typename T>
-inline const T* at(const void* p, size_t off) { return reinterpret_cast<const T*>(static_cast<const char*>(p) + off); }
-
 struct SpkShape {
   int M, H, L, E, W, S, math;
   int Hk;      // H rounded up to the 16-wide K chunk of the f16 MFMA

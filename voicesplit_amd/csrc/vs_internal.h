@@ -1,5 +1,6 @@
 // Prototypes of the per-kernel host launchers shared by capi.hip (inference orchestration) and
-// train.hip (training forward + backward orchestration).  Internal to libvoicesplit_hip.so.
+// train.hip (training forward + backward orchestration), and the small host helpers the
+// orchestration files share.  Internal to libvoicesplit_hip.so.
 #pragma once
 #include "vs_common.h"
 
@@ -22,6 +23,19 @@ struct VsTurnScope {
   ~VsTurnScope() { g_vs_turn = prev; }
 };
 inline int vs_det_grid(int nb, int cus = 256) { return (g_vs_turn && nb > cus) ? cus : nb; }      // deterministic mode: at most one workgroup per CU takes turns
+
+// ---- host helpers shared by the orchestration files (capi.hip, train.hip, loss.hip, speaker.hip) ----
+constexpr float kBnEps = 1e-5f;       // nn.BatchNorm2d default (models/voicesplit/model.py:19)
+constexpr float kBnMomentum = 0.1f;
+// conv-stack table (models/voicesplit/model.py:15-52): KT, KF, time dilation
+struct Spec { int kt, kf, dil; };
+constexpr Spec kMid[6] = {{7, 1, 1}, {5, 5, 1}, {5, 5, 2}, {5, 5, 4}, {5, 5, 8}, {5, 5, 16}};
+// every piece of a workspace / tape / scratch layout starts on a 256-byte boundary
+inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+template <typename T>
+inline T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+template <typename T>
+inline const T* at(const void* base, size_t off) { return reinterpret_cast<const T*>(static_cast<const char*>(base) + off); }
 
 // conv_mfma.hip
 int vs_conv64_pack_impl(const float* w, float* wp, int KT, int KF, int transpose_flip, hipStream_t);
@@ -227,11 +241,10 @@ struct VsLstmBf16Layout { size_t feat, wih, dxg, total; int Kp; };
 inline VsLstmBf16Layout vs_lstm_bf16_layout(long long M, int K, int H) {
   VsLstmBf16Layout L;
   L.Kp = (K + 63) / 64 * 64;
-  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
   L.feat = 0;
-  L.wih = up((size_t)M * L.Kp * 2);
-  L.dxg = L.wih + up((size_t)8 * H * L.Kp * 2);
-  L.total = L.dxg + up((size_t)M * 8 * H * 2);
+  L.wih = align_up((size_t)M * L.Kp * 2);
+  L.dxg = L.wih + align_up((size_t)8 * H * L.Kp * 2);
+  L.total = L.dxg + align_up((size_t)M * 8 * H * 2);
   return L;
 }
 // lstm.hip
