@@ -184,6 +184,35 @@ int vs_bilstm_fwd(const vs_dims* dims, const vs_params* params, const float* fea
 int vs_head_fwd(const vs_dims* dims, const vs_params* params, const float* lstm_out,
                 void* workspace, size_t workspace_bytes, float* logits, float* mask, void* stream);
 
+/* ---- eval-mode forward of a padded batch of clips of unequal length, each as if alone ---------------
+ * utils/generic_utils.py:476-558 runs validation / test sample by sample (B = 1) because its clips differ in length;
+ * models/voicesplit/model.py:66-89 on x[b, :lengths[b]] alone is what every item of these calls computes.
+ * x [B][T][F] with T = dims.T = the longest item, lengths [B]: DEVICE array, 1 <= lengths[b] <= T (the caller
+ * checks the range: the library cannot without a synchronisation, and clamps to [0, T] on the device so that no
+ * value can take a store out of bounds).  mask [B][T][FC2]: rows t < lengths[b] are those of the item alone (same
+ * kernels as vs_forward_prepared; the split-f16 operand scales are batch-wide, as in any batch), rows t >= lengths[b]
+ * are exactly 0.  The content of x's rows t >= lengths[b] is never read into the arithmetic (a copy of x with zeroed
+ * tails is what cnn1 and the |max| pass see): NaN there changes no bit of the result.
+ *   conv stack: the ZeroPad2d in time of cnn2..cnn7 (model.py:21-48) has to stand at each item's own end, so the
+ *     outputs of cnn1..cnn6 get their rows t >= lengths[b] zeroed (vs_zero_tail_rows) before the next layer reads them;
+ *   BiLSTM: nn.LSTM starts from a zero state at the item's first and LAST frame (model.py:82): the persistent
+ *     recurrence holds h = c = 0 while t >= lengths[b], in both directions;
+ *   head: runs over all B*T rows, then the mask's tail rows are zeroed.
+ * Eval mode only (BatchNorm running statistics), dims.math = VS_MATH_F16X3 or VS_MATH_BF16; VS_MATH_FP32 and a
+ * recurrence other than the tagged persistent kernel (H > 448, a grid that is not resident, vs_set_lstm_kernel != 0)
+ * are refused with an error, never computed some other way.  workspace: vs_workspace_bytes(dims), as for B x T. */
+int vs_forward_prepared_ragged(const vs_dims* dims, const vs_params* params, const void* prepared, size_t prepared_bytes,
+                               const float* x, const float* dvec, const int* lengths, int conv_act,
+                               void* workspace, size_t workspace_bytes, float* mask, void* stream);
+/* the stages of it: model.py:68-74 -> feat [B][T][8F] (rows t >= lengths[b]: finite, unspecified) and
+ * model.py:77-82 -> lstm_out [B][T][2H] (rows t >= lengths[b]: 0); weights derived per call, as in the stage calls above */
+int vs_conv_stack_fwd_ragged(const vs_dims* dims, const vs_params* params, const float* x, const int* lengths, int conv_act,
+                             void* workspace, size_t workspace_bytes, float* feat, void* stream);
+int vs_bilstm_fwd_ragged(const vs_dims* dims, const vs_params* params, const float* feat, const float* dvec, const int* lengths,
+                         void* workspace, size_t workspace_bytes, float* lstm_out, void* stream);
+/* ptr [B][T] rows of row_bytes bytes each (a multiple of 4; ptr 16-byte aligned): rows t >= lengths[b] of item b := 0 */
+int vs_zero_tail_rows(void* ptr, int B, int T, size_t row_bytes, const int* lengths, void* stream);
+
 /* ---- kernels (unit-test surface) --------------------------------------------------------- */
 /* BN(conv+bias) = conv*scale + shift */
 int vs_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,

@@ -83,6 +83,64 @@ def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg) -> torch.T
     return spec_to_wav(spec, phase, audio_cfg, mask=mask)
 
 
+# frames a ragged batch may occupy (items * longest item): 64 clips of 3 s, the batch the workspace of the 3 s path is sized for anyway
+RAGGED_MAX_ITEMS = 64
+RAGGED_MAX_FRAMES = 64 * 301
+
+
+def pad_specs(specs, device=None):
+    """List of [T_i, F] (or [1, T_i, F]) spectrograms -> (x [B, Tmax, F] zero padded, lengths list)."""
+    specs = [s.reshape(-1, s.shape[-1]) for s in specs]
+    lengths = [int(s.shape[0]) for s in specs]
+    x = torch.zeros(len(specs), max(lengths), specs[0].shape[1], dtype=specs[0].dtype, device=device or specs[0].device)
+    for b, s in enumerate(specs):
+        x[b, :lengths[b]] = s
+    return x, lengths
+
+
+def masks_ragged(model, specs, dvecs, max_items: int = RAGGED_MAX_ITEMS, max_frames: int = RAGGED_MAX_FRAMES):
+    """Masks of clips of unequal length through ``model.forward_ragged`` in planner batches: specs = list of [T_i, F],
+    dvecs [N, emb_dim] -> list of masks [T_i, fc2_dim], each what the model gives for that clip alone."""
+    from .streaming import plan_ragged_batches
+    lengths = [int(s.shape[0]) for s in specs]
+    out = [None] * len(specs)
+    with torch.no_grad():
+        for batch in plan_ragged_batches(lengths, max_items, max_frames):
+            x, lens = pad_specs([specs[i] for i in batch])
+            mask = model.forward_ragged(x, dvecs[batch].contiguous(), lens)
+            for b, i in enumerate(batch):
+                out[i] = mask[b, :lens[b]]
+    return out
+
+
+def separate_many(model, wavs, dvecs: torch.Tensor, audio_cfg, max_items: int = RAGGED_MAX_ITEMS, max_frames: int = RAGGED_MAX_FRAMES):
+    """``separate`` for clips of unequal length: wavs = list of 1-D waveforms (each a multiple of hop_length samples),
+    dvecs [N, emb_dim] -> list of estimated waveforms, each equal to ``separate`` on that clip alone.  The STFT reflects at each
+    clip's own ends and the iSTFT's envelope ends there, so front and back end run per group of clips of equal length; the
+    network runs on ragged batches of the whole list (``streaming.plan_ragged_batches``).  max_items / max_frames bound a batch
+    (clips, and clips x longest clip in frames): the workspace grows with the latter, about 0.36 MB per frame at full width."""
+    if len(wavs) != dvecs.shape[0]:
+        raise ValueError(f"{len(wavs)} waveforms for {dvecs.shape[0]} d-vectors")
+    groups = {}
+    for i, w in enumerate(wavs):
+        if w.dim() != 1:
+            raise ValueError(f"wavs[{i}]: expected a 1-D waveform, got {tuple(w.shape)}")
+        groups.setdefault(int(w.shape[0]), []).append(i)
+    specs, phases = [None] * len(wavs), [None] * len(wavs)
+    for idx in groups.values():
+        spec, phase = wav_to_spec(torch.stack([wavs[i] for i in idx]).contiguous(), audio_cfg)
+        for k, i in enumerate(idx):
+            specs[i], phases[i] = spec[k], phase[k]
+    masks = masks_ragged(model, specs, dvecs, max_items, max_frames)
+    out = [None] * len(wavs)
+    for idx in groups.values():
+        est = spec_to_wav(torch.stack([specs[i] for i in idx]), torch.stack([phases[i] for i in idx]), audio_cfg,
+                          mask=torch.stack([masks[i] for i in idx]))
+        for k, i in enumerate(idx):
+            out[i] = est[k]
+    return out
+
+
 def separate_with_reference(model, encoder, wav: torch.Tensor, ref_wavs, audio_cfg) -> torch.Tensor:
     """``separate`` with the d-vectors computed here from reference audio of the wanted speakers: ref_wavs = one 1-D
     waveform per row of wav (any length above n_fft / 2 samples and at least one encoder window of frames);

@@ -153,9 +153,11 @@ int prep_pointers(const vs_dims* d, const void* blob, size_t bytes, Prep* P) {
 }
 
 int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int conv_act, int bn_mode,
-                    void* ws, const vs_ws_layout& L, float* feat, hipStream_t stream, const Prep* prep, bool* feat_rows = nullptr);
+                    void* ws, const vs_ws_layout& L, float* feat, hipStream_t stream, const Prep* prep, bool* feat_rows = nullptr,
+                    const int* lengths = nullptr /* device [B]: the ragged eval forward, see vs_forward_prepared_ragged */);
 int bilstm_impl(const vs_dims* d, const vs_params* p, const float* feat, const float* dvec,
-                void* ws, const vs_ws_layout& L, float* lstm_out, hipStream_t stream, const Prep* prep, bool feat_rows = false);
+                void* ws, const vs_ws_layout& L, float* lstm_out, hipStream_t stream, const Prep* prep, bool feat_rows = false,
+                const int* lengths = nullptr);
 
 }  // namespace
 
@@ -613,7 +615,7 @@ int vs_conv_stack_fwd(const vs_dims* d, const vs_params* p, const float* x, int 
 
 namespace {
 int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int conv_act, int bn_mode,
-                    void* ws, const vs_ws_layout& L, float* feat, hipStream_t stream, const Prep* prep, bool* feat_rows) {
+                    void* ws, const vs_ws_layout& L, float* feat, hipStream_t stream, const Prep* prep, bool* feat_rows, const int* lengths) {
   VS_REQUIRE(p && x, "conv_stack: NULL argument");
   if (feat_rows) *feat_rows = false;
   VS_REQUIRE(conv_act == VS_ACT_MISH || conv_act == VS_ACT_RELU, "conv_stack: conv_act must be MISH or RELU");
@@ -626,6 +628,24 @@ int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int co
   double* stats = at<double>(ws, L.bn_stats);
   const bool train = bn_mode == VS_BN_TRAIN;
   VS_REQUIRE(!(prep && train), "conv_stack: prepared weights are an eval-mode form (BatchNorm folded)");
+  // Ragged batch (lengths != NULL): every layer with extent in time (cnn2 7x1, cnn3..cnn7 5x5 dilated) must see ZEROS behind each item's
+  // own end, as its ZeroPad2d gives the item alone.  So x is read from a copy with zeroed tails (in the feature region: cnn8 writes it only
+  // when cnn1 is long done, or never), and the outputs of cnn1..cnn6 get their tail rows zeroed before the next layer reads them -- one
+  // sweep per layer over the channels-last tensor(s).  The convs themselves run over all B*T rows (no row-group skipping: see DESIGN.md
+  // 6.8b); the |max| that the split-f16 layers track therefore includes the finite tail rows they computed, which moves a power-of-two
+  // operand scale at most, as a batch mate does.  cnn7's and cnn8's tails stay: nothing behind them looks across rows.
+  VS_REQUIRE(!lengths || (!train && d->math != VS_MATH_FP32),
+             "conv_stack: per-item lengths are served in eval mode by the channels-last arithmetics (VS_MATH_F16X3, VS_MATH_BF16), not by %s",
+             train ? "train mode" : "VS_MATH_FP32");
+  if (lengths) {
+    float* xz = at<float>(ws, L.feat);
+    VS_CHECK_HIP(hipMemcpyAsync(xz, x, sizeof(float) * (size_t)d->B * d->T * d->F, hipMemcpyDeviceToDevice, stream));
+    if (int rc = vs_zero_tail_rows_impl(xz, d->B, d->T, sizeof(float) * (size_t)d->F, lengths, stream)) return rc;
+    x = xz;
+  }
+  auto zero_tails = [&](void* a, size_t row_bytes) -> int {
+    return lengths ? vs_zero_tail_rows_impl(a, d->B, d->T, row_bytes, lengths, stream) : 0;
+  };
 
   for (int l = 0; l < 8; ++l) {
     const vs_conv_layer& c = p->conv[l];
@@ -678,6 +698,7 @@ int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int co
                                          kBnMomentum, scale, shift, nullptr, nullptr, stream)) return rc;
         if (int rc = vs_nhwc_conv_first_impl(x, cl.weight, scale, shift, abuf[c], B, T, F, conv_act, nullptr, stream, cl.bias)) return rc;
       } else if (int rc = vs_nhwc_conv_first_impl(x, p->conv[0].weight, scale, shift, abuf[c], B, T, F, layer_act, nullptr, stream)) return rc;
+      if (int rc = zero_tails(abuf[c], (size_t)F * 64 * 2)) return rc;
     }
     for (int i = 0; i < 6; ++i) {
       const int l = i + 1;
@@ -689,6 +710,7 @@ int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int co
                                      kMid[i].dil, layer_act, train ? stats : nullptr, stream)) return rc;
       c ^= 1;
       if (train) { if (int rc = bn_train(l, abuf[c])) return rc; }
+      if (l < 6) { if (int rc = zero_tails(abuf[c], (size_t)F * 64 * 2)) return rc; }
     }
     ProfScope ps(VS_PROF_CNN8, stream);
     // the whole-path eval forward (feat_rows != NULL: nobody reads the fp32 features): cnn8 writes the bf16 A operand of the LSTM input
@@ -723,6 +745,8 @@ int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int co
       if (int rc = vs_nhwc_first_plan_impl(vs_amax_slot(slot(0)), 1, p->conv[0].weight, scale, shift, slot(1), stream)) return rc;
       if (int rc = vs_nhwc_conv_first_split_impl(x, p->conv[0].weight, scale, shift, slot(1), plane[0][0], plane[0][1], vs_amax_slot(slot(1)),
                                                  B, T, F, layer_act, stream)) return rc;
+      if (int rc = zero_tails(plane[0][0], (size_t)F * 64 * 2)) return rc;
+      if (int rc = zero_tails(plane[0][1], (size_t)F * 64 * 2)) return rc;
     }
     // the whole-path forward (feat_rows != NULL: nobody reads the fp32 features): cnn8 writes the LSTM input GEMM's split A operand
     // into the idle ping-pong buffer, at a scale planned from the tracked |max| of its input -- no fp32 features, no |max| and split passes
@@ -742,6 +766,10 @@ int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int co
                                             slot(l + 1), (l < 6 || rows) ? vs_amax_slot(slot(l + 1)) : nullptr, B, T, F, kMid[i].kt, kMid[i].kf,
                                             kMid[i].dil, layer_act, stream)) return rc;
       c ^= 1;
+      if (l < 6) {
+        if (int rc = zero_tails(plane[c][0], (size_t)F * 64 * 2)) return rc;
+        if (int rc = zero_tails(plane[c][1], (size_t)F * 64 * 2)) return rc;
+      }
     }
     ProfScope ps(VS_PROF_CNN8, stream);
     if (rows) {      // six layers: c == 0, the input planes fill act0 and act1 is idle
@@ -827,7 +855,7 @@ int vs_bilstm_fwd(const vs_dims* d, const vs_params* p, const float* feat, const
 
 namespace {
 int bilstm_impl(const vs_dims* d, const vs_params* p, const float* feat, const float* dvec,
-                void* ws, const vs_ws_layout& L, float* lstm_out, hipStream_t stream, const Prep* prep, bool feat_rows) {
+                void* ws, const vs_ws_layout& L, float* lstm_out, hipStream_t stream, const Prep* prep, bool feat_rows, const int* lengths) {
   VS_REQUIRE(p && dvec, "bilstm: NULL argument");
   if (!feat) feat = at<float>(ws, L.feat);
   if (!lstm_out) lstm_out = at<float>(ws, L.lstm_out);
@@ -857,7 +885,8 @@ int bilstm_impl(const vs_dims* d, const vs_params* p, const float* feat, const f
   float* packed = prep ? prep->lstm_packed : at<float>(ws, L.lstm_packed);
   if (!prep) { if (int rc = vs_lstm_pack_impl(p->w_hh[0], p->w_hh[1], packed, H, stream, d->math)) return rc; }
   ProfScope ps(VS_PROF_LSTM_REC, stream);
-  return vs_bilstm_recurrent_impl(xg, packed, at<float>(ws, L.lstm_state), lstm_out, nullptr, nullptr, B, T, H, stream, d->math);
+  // (lengths: the input GEMM above ran over all B*T rows; the recurrence keeps the rows behind an item's end out of its state)
+  return vs_bilstm_recurrent_impl(xg, packed, at<float>(ws, L.lstm_state), lstm_out, nullptr, nullptr, B, T, H, stream, d->math, lengths);
 }
 }  // namespace
 
@@ -985,6 +1014,55 @@ int vs_forward_prepared(const vs_dims* d, const vs_params* p, const void* prepar
   if (int rc = conv_stack_impl(d, p, x, conv_act, VS_BN_EVAL, ws, L, nullptr, (hipStream_t)stream, &P, &feat_rows)) return rc;
   if (int rc = bilstm_impl(d, p, nullptr, dvec, ws, L, nullptr, (hipStream_t)stream, &P, feat_rows)) return rc;
   return head_fwd_impl(d, p, nullptr, ws, ws_bytes, nullptr, mask, (hipStream_t)stream, P.head_packed);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the same forward on a padded batch of clips of unequal length, each as if alone (see the header)
+// ---------------------------------------------------------------------------------------------
+static int check_ragged(const vs_dims* d, const int* lengths, const char* what) {
+  if (int rc = check_dims(d)) return rc;
+  VS_REQUIRE(lengths != nullptr, "%s: lengths is NULL", what);
+  VS_REQUIRE(d->math == VS_MATH_F16X3 || d->math == VS_MATH_BF16,
+             "%s: per-item lengths are served by VS_MATH_F16X3 and VS_MATH_BF16; VS_MATH_FP32 has no ragged route", what);
+  return 0;
+}
+
+int vs_forward_prepared_ragged(const vs_dims* d, const vs_params* p, const void* prepared, size_t prepared_bytes,
+                               const float* x, const float* dvec, const int* lengths, int conv_act,
+                               void* ws, size_t ws_bytes, float* mask, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VS_REQUIRE(mask != nullptr, "forward_prepared_ragged: mask is NULL");
+  if (int rc = check_ragged(d, lengths, "forward_prepared_ragged")) return rc;
+  Prep P;
+  if (int rc = prep_pointers(d, prepared, prepared_bytes, &P)) return rc;
+  vs_ws_layout L;
+  if (int rc = check_ws(d, ws, ws_bytes, &L)) return rc;
+  bool feat_rows = false;
+  if (int rc = conv_stack_impl(d, p, x, conv_act, VS_BN_EVAL, ws, L, nullptr, stream, &P, &feat_rows, lengths)) return rc;
+  if (int rc = bilstm_impl(d, p, nullptr, dvec, ws, L, nullptr, stream, &P, feat_rows, lengths)) return rc;
+  if (int rc = head_fwd_impl(d, p, nullptr, ws, ws_bytes, nullptr, mask, stream, P.head_packed)) return rc;
+  // the head ran over all B*T rows (a zero LSTM row still gives sigmoid(bias terms)): the mask's tail rows are stored as zeros here
+  return vs_zero_tail_rows_impl(mask, d->B, d->T, sizeof(float) * (size_t)d->FC2, lengths, stream);
+}
+
+int vs_conv_stack_fwd_ragged(const vs_dims* d, const vs_params* p, const float* x, const int* lengths, int conv_act,
+                             void* ws, size_t ws_bytes, float* feat, void* stream_) {
+  if (int rc = check_ragged(d, lengths, "conv_stack_fwd_ragged")) return rc;
+  vs_ws_layout L;
+  if (int rc = check_ws(d, ws, ws_bytes, &L)) return rc;
+  return conv_stack_impl(d, p, x, conv_act, VS_BN_EVAL, ws, L, feat, (hipStream_t)stream_, nullptr, nullptr, lengths);
+}
+
+int vs_bilstm_fwd_ragged(const vs_dims* d, const vs_params* p, const float* feat, const float* dvec, const int* lengths,
+                         void* ws, size_t ws_bytes, float* lstm_out, void* stream_) {
+  if (int rc = check_ragged(d, lengths, "bilstm_fwd_ragged")) return rc;
+  vs_ws_layout L;
+  if (int rc = check_ws(d, ws, ws_bytes, &L)) return rc;
+  return bilstm_impl(d, p, feat, dvec, ws, L, lstm_out, (hipStream_t)stream_, nullptr, false, lengths);
+}
+
+int vs_zero_tail_rows(void* ptr, int B, int T, size_t row_bytes, const int* lengths, void* stream) {
+  return vs_zero_tail_rows_impl(ptr, B, T, row_bytes, lengths, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

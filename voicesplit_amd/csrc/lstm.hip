@@ -1000,9 +1000,13 @@ void lstm16_persistent_kernel(Lstm16Args a) {
 // ---------------------------------------------------------------------------------------------
 constexpr unsigned kSentinel = 0x7FFF7FFFu;
 
-template <int NP>
+// RAGGED (the eval forward of a padded batch of clips of unequal length, vs_bilstm_fwd_ragged): wave 0's gate arithmetic holds
+// h = c = 0 while t >= lengths[b] -- two selects per gate lane, the same schedule and hand-off.  The reverse direction then reaches
+// t = lengths[b] - 1 with the zero state of a fresh clip, the forward direction writes zeros past the end.  Selects, not products:
+// whatever xg holds in those rows (NaN included) stays out.  !RAGGED is the kernel as it was (lengths unused).
+template <int NP, bool RAGGED>
 __global__ __launch_bounds__(256)
-void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3) {
+void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __restrict__ lengths) {
   __shared__ float sRed[2][3 * 16 * 64];      // by step parity: no barrier separates wave 0's reads of step s from the other waves' writes of step s + 1
   __shared__ int sDead;
   const int tid = threadIdx.x;
@@ -1041,6 +1045,8 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3) {
   const unsigned slot_off = (unsigned)((((group * NC + (jg >> 1)) * NP + plane) * 64 + (jg & 1) * 32 + l31) * 16);
   const bool storer = NP == 2 || half == 0;
   float cprev[4] = {0.f, 0.f, 0.f, 0.f};
+  int len = a.T;
+  if (RAGGED) len = b < a.B ? lengths[b] : 0;
   __syncthreads();
 
 #pragma unroll 1
@@ -1116,8 +1122,12 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3) {
         const float gf = vs_sigmoid_fast(fmaf(acc[4 + u], inv, xgv[4 + u]));
         const float gg = vs_tanh_fast(fmaf(acc[8 + u], inv, xgv[8 + u]));
         const float go = vs_sigmoid_fast(fmaf(acc[12 + u], inv, xgv[12 + u]));
-        const float cn = gf * cprev[u] + gi * gg;
+        float cn = gf * cprev[u] + gi * gg;
         hv[u] = go * vs_tanh_fast(cn);
+        if (RAGGED) {
+          cn = t < len ? cn : 0.f;
+          hv[u] = t < len ? hv[u] : 0.f;
+        }
         cnew[u] = cn;
         cprev[u] = cn;
         gact[0][u] = gi; gact[1][u] = gf; gact[2][u] = gg; gact[3][u] = go;
@@ -1409,7 +1419,7 @@ hipError_t launch_resident(const void* kernel, dim3 grid, dim3 block, Args& a, h
 // state: 3 * [2][H][Bpad] floats.  Step kernels: h ping, h pong, c, zeroed here (zero initial state).
 // Persistent kernel: h ping, h pong (fragment order), then the flag words + the error word.
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
-                             int B, int T, int H, hipStream_t stream, int math) {
+                             int B, int T, int H, hipStream_t stream, int math, const int* lengths) {
   VS_REQUIRE(B > 0 && T > 0 && H > 0 && H % 8 == 0, "lstm: bad shape B=%d T=%d H=%d (H must be a multiple of 8)", B, T, H);
   const int Bpad = (B + 31) / 32 * 32;
   const size_t per = lstm_state_region(B, H);
@@ -1427,6 +1437,10 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
   // the tagged-data hand-off of the f16 forward recurrence: three exchange buffers (the regions of h ping, h pong and of the flags),
   // the second and third armed with the sentinel
   const bool tagged = persistent && math != VS_MATH_CODE_FP32 && g_lstm_kernel != 4 && (H + 15) / 16 <= 4 * kMaxC;
+  // per-item lengths: the tagged kernel is the one recurrence that takes them; anything else is refused, not computed some other way
+  VS_REQUIRE(!lengths || (tagged && !gates_save && !c_save),
+             "lstm: per-item lengths need the tagged persistent recurrence in eval mode (dims.math F16X3 or BF16, H <= %d, 2*H/8 = %d workgroups "
+             "<= %d CUs, vs_set_lstm_kernel 0 or 2); VS_MATH_FP32, the flag kernel and the per-step kernels do not take them", 64 * kMaxC, 2 * HQ, cus);
   if (tagged) VS_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(state + per), (int)kSentinel, 3 * per, stream));
   if (persistent) {
     unsigned* flags = reinterpret_cast<unsigned*>(state + 2 * per);      // zeroed above
@@ -1446,10 +1460,11 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
         if (tagged) {
           void* hb2 = state + 2 * per;
           void* hb3 = state + 3 * per;
-          void* params[] = {&a, &hb2, &hb3};
-          e = hipLaunchCooperativeKernel(math == VS_MATH_CODE_BF16 ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<1>)
-                                                                   : reinterpret_cast<const void*>(&lstm16_tagged_kernel<2>),
-                                         dim3(HQ * nbt, 2), dim3(256), params, 0, stream);
+          void* params[] = {&a, &hb2, &hb3, &lengths};
+          const void* kernel = math == VS_MATH_CODE_BF16
+              ? (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, false>))
+              : (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, false>));
+          e = hipLaunchCooperativeKernel(kernel, dim3(HQ * nbt, 2), dim3(256), params, 0, stream);
         } else
         e = math == VS_MATH_CODE_BF16
                 ? launch_resident(reinterpret_cast<const void*>(&lstm16_persistent_kernel<1>), dim3(HQ * nbt, 2), dim3(256), a, stream)
@@ -1459,6 +1474,8 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
         (void)hipGetLastError();
         // refused before anything ran (first launch): the step kernels below do the whole job; later: an error
         VS_REQUIRE(bt0 == 0 && g_lstm_kernel != 2, "lstm: persistent recurrence could not be launched resident: %s", hipGetErrorString(e));
+        VS_REQUIRE(!lengths, "lstm: per-item lengths: the persistent recurrence could not be launched resident (%s) and the per-step kernels do not take them",
+                   hipGetErrorString(e));
         launched = false;
         break;
       }

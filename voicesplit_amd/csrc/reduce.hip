@@ -1,5 +1,6 @@
 // Small streaming kernels of the backward pass: the sigmoid gradient of the mask head and the
-// column sums that produce bias gradients (models/voicesplit/model.py:83-87 backwards).
+// column sums that produce bias gradients (models/voicesplit/model.py:83-87 backwards); and the
+// tail sweep of the ragged eval forward (rows past each item's own length := 0).
 #include "vs_common.h"
 
 namespace {
@@ -55,7 +56,52 @@ void colsum_kernel(const float* __restrict__ x, int ld, int rows, int N, float* 
   out[(size_t)blockIdx.y * ldo + n] = (s0 + s1) + (s2 + s3);
 }
 
+// Rows t >= lengths[b] of item b of a [B][T] array of rows of `row_words` dwords := 0.  Channels-last layouts: the tail of an item is ONE
+// contiguous block of (T - len) * row_words dwords.  Workgroup (x, b) owns the x-th piece of kZeroChunk dwords of item b's tail and
+// leaves at once when the tail ends in front of it (short-lived workgroups, 16-byte stores, no grid-stride loop: DESIGN.md 6.4); the
+// grid is sized for the longest tail the clamp allows, T rows.  Up to three dwords on either side of the 16-byte aligned body (rows of
+// FC2 = 601 floats) are stored singly by the first workgroup of the item.  lengths[b] is clamped to [0, T]: nothing can leave the array.
+constexpr int kZeroVecs = 4;                            // 16-byte stores per thread
+constexpr long long kZeroChunk = 256 * kZeroVecs * 4;   // dwords per workgroup
+
+__global__ __launch_bounds__(256)
+void zero_tail_rows_kernel(unsigned* __restrict__ p, int T, long long row_words, const int* __restrict__ lengths) {
+  const int b = blockIdx.y;
+  int len = lengths[b];
+  len = len < 0 ? 0 : (len > T ? T : len);
+  const long long begin = ((long long)b * T + len) * row_words, end = (long long)(b + 1) * T * row_words;
+  const long long body = (begin + 3) & ~3LL;            // first dword on a 16-byte boundary (p itself is aligned)
+  const long long first = body + (long long)blockIdx.x * kZeroChunk;
+  if (first >= end && blockIdx.x > 0) return;
+  if (blockIdx.x == 0) {
+    const long long head_end = body < end ? body : end;
+    if (begin + threadIdx.x < head_end && threadIdx.x < 3) p[begin + threadIdx.x] = 0u;
+    const long long tail_begin = end & ~3LL;             // dwords behind the last whole vector
+    if (threadIdx.x >= 64 && threadIdx.x < 67) {
+      const long long i = (tail_begin > body ? tail_begin : body) + (threadIdx.x - 64);
+      if (i < end) p[i] = 0u;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < kZeroVecs; ++v) {
+    const long long i = first + ((long long)v * 256 + threadIdx.x) * 4;
+    if (i + 4 <= end) *reinterpret_cast<uint4*>(p + i) = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
 }  // namespace
+
+int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t stream) {
+  VS_REQUIRE(ptr && lengths, "zero_tail_rows: NULL argument");
+  VS_REQUIRE(B > 0 && B <= 65535 && T > 0 && row_bytes > 0 && row_bytes % 4 == 0, "zero_tail_rows: bad shape B=%d T=%d row_bytes=%zu", B, T, row_bytes);
+  VS_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & 15) == 0, "zero_tail_rows: the array must be 16-byte aligned");
+  const long long row_words = (long long)(row_bytes / 4);
+  const long long nb = ((long long)T * row_words + kZeroChunk - 1) / kZeroChunk;
+  VS_REQUIRE(nb < 2147483647LL, "zero_tail_rows: array too large");
+  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, stream, static_cast<unsigned*>(ptr), T, row_words, lengths);
+  VS_LAUNCH_CHECK();
+  return 0;
+}
 
 int vs_sigmoid_bwd_impl(const float* dmask, const float* mask, float* dlogits, long long n, hipStream_t stream) {
   VS_REQUIRE(n > 0, "sigmoid_bwd: n=%lld", n);

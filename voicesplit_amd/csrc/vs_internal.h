@@ -252,7 +252,8 @@ inline VsLstmBf16Layout vs_lstm_bf16_layout(long long M, int K, int H) {
 // (BPTT, VS_MATH_BF16 only) bf16; the pack calls write the matching operand form behind the fp32 one
 int vs_lstm_pack_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
-                             int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32);
+                             int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32,
+                             const int* lengths = nullptr /* device [B]: h = c = 0 while t >= lengths[b]; only the tagged persistent kernel takes them */);
 int vs_lstm_pack_t_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
 int vs_bilstm_bwd_recurrent_impl(const float* wpt, float* state, float* gates, const float* c_all, const float* dout,
                                  int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32);
@@ -260,3 +261,5 @@ int vs_bilstm_bwd_recurrent_impl(const float* wpt, float* state, float* gates, c
 int vs_sigmoid_bwd_impl(const float* dmask, const float* mask, float* dlogits, long long n, hipStream_t);
 int vs_sigmoid_bwd_rows_impl(const float* dmask, const float* mask, float* dlogits, long long rows, int N, void* rows_bf16, int Kp, hipStream_t);
 int vs_colsum_impl(const float* x, int ld, int groups, int rows, int N, float* out, int ldo, hipStream_t);
+// rows t >= lengths[b] of a [B][T][row_bytes] array := 0 (the ragged eval forward: capi.hip)
+int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t);

@@ -13,6 +13,11 @@ the target and mixed waveforms (``c.dataset['format']``); the mixture's spectrog
 come from the GPU front end (``audio.wav_to_spec``), the estimate from ``audio.spec_to_wav`` and the SDR from
 ``metrics.bss_sdr`` -- the whole of ``validation(test=True)`` (utils/generic_utils.py:476-530) on the device, in batches of
 ``c.test_config['batch_size']`` items (which must share a length).  Scores are ``Trainer.evaluate``'s.
+
+``--ragged``: the items may differ in length (the reference's own test sets do, which is why it scores them one by one).
+Batches of at most ``batch_size`` items are planned over the whole set by length (``streaming.plan_ragged_batches``), the
+network runs each padded batch with every item computed as if alone (``model.forward_ragged``), and loss and SDR are taken
+per item at its own length and averaged over items (``Trainer.evaluate_ragged``).
 """
 import argparse
 import json
@@ -48,12 +53,44 @@ class EvalDataset:
                 (self.emb[i], self.target_wav[i], self.mixed_wav[i]))
 
 
-def eval_batches(c, ds: EvalDataset, device):
+def _ragged_batches(c, ds: EvalDataset, device, bs: int):
+    """``Trainer.evaluate_ragged``'s batches over the whole set: at most ``bs`` items each, grouped by length."""
+    from . import audio
+    from .streaming import plan_ragged_batches
+    acfg = c.audio[c.audio["backend"]]
+    hop = int(acfg["hop_length"])
+    items = [it for it in (ds[i] for i in range(len(ds))) if it[0].tolist() != [0]]
+    for it in items:
+        if it[1].shape[0] != it[2].shape[0]:
+            raise ValueError(f"target and mixture differ in length: {os.path.basename(it[3][1])} ({it[1].shape[0]}) / "
+                             f"{os.path.basename(it[3][2])} ({it[2].shape[0]})")
+    if not items:
+        return
+    frames = [audio.frames_for(it[2].shape[0], hop) for it in items]
+    for batch in plan_ragged_batches(frames, bs, bs * max(frames)):
+        specs = []
+        for i in batch:                                   # the STFT reflects at the clip's own ends: front end per item
+            mixed, phase = audio.wav_to_spec(items[i][2].to(device).reshape(1, -1), acfg, want_phase=True)
+            target, _ = audio.wav_to_spec(items[i][1].to(device).reshape(1, -1), acfg, want_phase=False)
+            specs.append((mixed[0], phase[0], target[0]))
+        mixed, lens = audio.pad_specs([s[0] for s in specs])
+        phase, _ = audio.pad_specs([s[1] for s in specs])
+        target, _ = audio.pad_specs([s[2] for s in specs])
+        emb = torch.stack([items[i][0].float().reshape(-1) for i in batch]).to(device)
+        seq_len = torch.tensor([items[i][2].shape[0] for i in batch], dtype=torch.int32, device=device)
+        yield emb, target, mixed, seq_len, [items[i][1] for i in batch], phase, lens
+
+
+def eval_batches(c, ds: EvalDataset, device, ragged: bool = False):
     """``Trainer.evaluate``'s batches: (emb, target_spec, mixed_spec, seq_len, target_wav (host), mixed_phase), in dataset
-    order, ``c.test_config['batch_size']`` items each; items whose embedding is [0] are dropped (utils/dataset.py:93-95)."""
+    order, ``c.test_config['batch_size']`` items each; items whose embedding is [0] are dropped (utils/dataset.py:93-95).
+    ragged: ``Trainer.evaluate_ragged``'s batches instead -- items of any length, planned over the whole set."""
     from . import audio
     acfg = c.audio[c.audio["backend"]]
     bs = int(c["test_config"]["batch_size"]) if "test_config" in c else 1          # config.json:33-36 (1 when absent)
+    if ragged:
+        yield from _ragged_batches(c, ds, device, bs)
+        return
     for lo in range(0, len(ds), bs):
         items = [ds[i] for i in range(lo, min(lo + bs, len(ds)))]
         items = [it for it in items if it[0].tolist() != [0]]
@@ -84,9 +121,11 @@ def build_trainer(c, device) -> Trainer:
     return Trainer(model.to(device), c)
 
 
-def score_checkpoint(tr: Trainer, path: str, ds: EvalDataset, device):
+def score_checkpoint(tr: Trainer, path: str, ds: EvalDataset, device, ragged: bool = False):
     """(mean_loss, mean_sdr) of one checkpoint (test.py:test + validation(test=True))."""
     tr.load_checkpoint(path)
+    if ragged:
+        return tr.evaluate_ragged(eval_batches(tr.c, ds, device, ragged=True))
     return tr.evaluate(eval_batches(tr.c, ds, device))
 
 
@@ -99,6 +138,8 @@ def main(argv=None):
     which.add_argument("--checkpoint_path", help="one checkpoint (test.py)")
     which.add_argument("--checkpoints_path", help="a directory of checkpoints (test_all_checkpoints.py)")
     ap.add_argument("--json", default=None, help="--checkpoints_path: where the per-checkpoint table goes")
+    ap.add_argument("--ragged", action="store_true",
+                    help="test items may differ in length: ragged batches, loss and SDR per item at its own length")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("voicesplit_amd.evaluate needs a GPU: the evaluation path has no CPU implementation")
@@ -108,7 +149,7 @@ def main(argv=None):
     ds = EvalDataset(c, args.dataset_dir)
     tr = build_trainer(c, dev)
     if args.checkpoint_path:
-        mean_loss, mean_sdr = score_checkpoint(tr, args.checkpoint_path, ds, dev)
+        mean_loss, mean_sdr = score_checkpoint(tr, args.checkpoint_path, ds, dev, ragged=args.ragged)
         print("Mean Test Loss:", mean_loss)
         print("Mean Test SDR:", mean_sdr)
         return mean_loss, mean_sdr
@@ -117,7 +158,7 @@ def main(argv=None):
         raise FileNotFoundError(f"no *.pt checkpoints in {args.checkpoints_path}")
     table = []
     for p in paths:
-        mean_loss, mean_sdr = score_checkpoint(tr, p, ds, dev)
+        mean_loss, mean_sdr = score_checkpoint(tr, p, ds, dev, ragged=args.ragged)
         print(f"{p}: Mean Test Loss: {mean_loss} Mean Test SDR: {mean_sdr}", flush=True)
         table.append({"checkpoint": p, "mean_sdr": mean_sdr, "mean_loss": mean_loss})
     scored = [t for t in table if t["mean_sdr"] == t["mean_sdr"]]          # NaN: no item of the set could be scored

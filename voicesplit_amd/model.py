@@ -275,6 +275,28 @@ class _MaskNet(nn.Module):
 
         return conv_stage, sequence_stage
 
+    def forward_ragged(self, x, speaker_embedding, lengths):
+        """A padded batch of clips of unequal length, each as if alone: x [B, Tmax, num_freq], lengths [B] (sequence or
+        tensor, 1 <= lengths[b] <= Tmax) -> mask [B, Tmax, fc2_dim] whose rows t < lengths[b] are
+        ``self(x[b:b+1, :lengths[b]], speaker_embedding[b:b+1])`` (the conv stack zero-pads in time at each item's own end, the
+        BiLSTM starts from a zero state at its own first and last frame) and whose rows t >= lengths[b] are exactly 0.
+        What x holds in those rows does not matter.  Inference only: eval mode, no autograd.  The range of ``lengths`` is checked
+        on the host before anything is launched (the library cannot check a device array without a synchronisation): pass a
+        list or a CPU tensor; a tensor on the device is copied back first, which synchronises the stream."""
+        if self.training:
+            raise RuntimeError("forward_ragged runs in eval mode (BatchNorm running statistics, no tape): call model.eval() first")
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_ragged produces no gradients: call it under torch.no_grad()")
+        x = x.contiguous()
+        dvec = speaker_embedding.contiguous()
+        dims = self._dims(x.shape[0], x.shape[1])
+        sd = self._tensors()
+        prep = self.__dict__.get("_prepared")
+        if prep is None or not prep.matches(sd, dims):
+            prep = ops.PreparedWeights(sd, dims)
+            self.__dict__["_prepared"] = prep
+        return ops.forward_prepared(sd, prep, x, dvec, dims, self.conv_act, lengths=lengths)
+
     def forward(self, x, speaker_embedding):
         # x: [B, T, num_freq]; speaker_embedding: [B, emb_dim]  ->  mask [B, T, fc2_dim]
         if torch.is_grad_enabled() and x.requires_grad:

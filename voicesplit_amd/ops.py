@@ -183,15 +183,35 @@ class PreparedWeights:
         return self.key == self._key(sd, dims)
 
 
+def device_lengths(lengths, B: int, T: int, device) -> torch.Tensor:
+    """lengths (sequence or tensor, any device) -> int32 [B] on ``device`` after the range check the library leaves to its
+    caller: every item has 1 <= length <= T.  (Reads the values on the host: a tensor on the device is synchronised.)"""
+    host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    if len(host) != B:
+        raise ValueError(f"lengths: {len(host)} values for a batch of {B}")
+    bad = [(i, v) for i, v in enumerate(host) if v < 1 or v > T]
+    if bad:
+        raise ValueError(f"lengths: every item needs 1 <= length <= T = {T}; got " + ", ".join(f"lengths[{i}] = {v}" for i, v in bad[:4]))
+    return torch.tensor(host, dtype=torch.int32, device=device)
+
+
 def forward_prepared(sd, prepared: PreparedWeights, x, dvec, dims: VsDims, conv_act: str,
-                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     workspace: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
     """Eval-mode mask = model(x, dvec) with the weight-only work read from ``prepared``; bit-identical to
-    ``forward(..., training=False)``."""
+    ``forward(..., training=False)``.  lengths (one per item, 1..T): the padded batch x holds clips of unequal length and
+    every item is computed as if alone (vs_forward_prepared_ragged); mask rows past an item's length are 0."""
     lib = _lib.load()
     _check_inputs(x, dvec, dims)
     params = pack_params(sd)
     ws = workspace if workspace is not None else get_workspace(dims, x.device)
     mask = torch.empty(dims.B, dims.T, dims.FC2, dtype=torch.float32, device=x.device)
+    if lengths is not None:
+        lens = device_lengths(lengths, dims.B, dims.T, x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.vs_forward_prepared_ragged(ctypes.byref(dims), ctypes.byref(params), _p(prepared.buf), prepared.buf.numel(),
+                                                _p(x), _p(dvec), _p(lens), ACT_CODES[conv_act], _p(ws), ws.numel(), _p(mask), _stream())
+        check(rc, "vs_forward_prepared_ragged")
+        return mask
     with torch.cuda.device(x.device):
         rc = lib.vs_forward_prepared(ctypes.byref(dims), ctypes.byref(params), _p(prepared.buf), prepared.buf.numel(),
                                      _p(x), _p(dvec), ACT_CODES[conv_act], _p(ws), ws.numel(), _p(mask), _stream())
@@ -212,6 +232,21 @@ def conv_stack(sd, x, dims: VsDims, conv_act: str, training: bool = False, works
     return feat
 
 
+def conv_stack_ragged(sd, x, lengths, dims: VsDims, conv_act: str, workspace=None) -> torch.Tensor:
+    """Eval-mode features of a padded batch, rows t < lengths[b] as of the item alone (rows behind: finite, unspecified)."""
+    lib = _lib.load()
+    _dev_check(x, "x")
+    params = pack_params(sd)
+    lens = device_lengths(lengths, dims.B, dims.T, x.device)
+    ws = workspace if workspace is not None else get_workspace(dims, x.device)
+    feat = torch.empty(dims.B, dims.T, 8 * dims.F, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.vs_conv_stack_fwd_ragged(ctypes.byref(dims), ctypes.byref(params), _p(x), _p(lens), ACT_CODES[conv_act],
+                                          _p(ws), ws.numel(), _p(feat), _stream())
+    check(rc, "vs_conv_stack_fwd_ragged")
+    return feat
+
+
 def bilstm(sd, feat, dvec, dims: VsDims, workspace=None) -> torch.Tensor:
     lib = _lib.load()
     _dev_check(feat, "feat")
@@ -224,6 +259,35 @@ def bilstm(sd, feat, dvec, dims: VsDims, workspace=None) -> torch.Tensor:
                                _p(out), _stream())
     check(rc, "vs_bilstm_fwd")
     return out
+
+
+def bilstm_ragged(sd, feat, dvec, lengths, dims: VsDims, workspace=None) -> torch.Tensor:
+    """BiLSTM of a padded batch with a zero state at each item's own first and last frame; rows t >= lengths[b] are 0."""
+    lib = _lib.load()
+    _dev_check(feat, "feat")
+    _dev_check(dvec, "speaker_embedding")
+    params = pack_params(sd)
+    lens = device_lengths(lengths, dims.B, dims.T, feat.device)
+    ws = workspace if workspace is not None else get_workspace(dims, feat.device)
+    out = torch.empty(dims.B, dims.T, 2 * dims.H, dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device):
+        rc = lib.vs_bilstm_fwd_ragged(ctypes.byref(dims), ctypes.byref(params), _p(feat), _p(dvec), _p(lens), _p(ws), ws.numel(),
+                                      _p(out), _stream())
+    check(rc, "vs_bilstm_fwd_ragged")
+    return out
+
+
+def zero_tail_rows(t: torch.Tensor, lengths) -> torch.Tensor:
+    """In place: rows t[b, lengths[b]:] := 0 of a contiguous [B, T, ...] tensor (vs_zero_tail_rows; unit-test surface)."""
+    lib = _lib.load()
+    _dev_check(t, "t", t.dtype)
+    B, T = t.shape[0], t.shape[1]
+    row_bytes = (t[0, 0].numel() if t.dim() > 2 else 1) * t.element_size()
+    lens = device_lengths(lengths, B, T, t.device)
+    with torch.cuda.device(t.device):
+        rc = lib.vs_zero_tail_rows(_p(t), B, T, row_bytes, _p(lens), _stream())
+    check(rc, "vs_zero_tail_rows")
+    return t
 
 
 def head(sd, lstm_out, dims: VsDims, want_logits: bool = False, workspace=None):

@@ -158,3 +158,33 @@ def separate_long_exact(conv_stage: Callable[[torch.Tensor], torch.Tensor],
             pos += n
         assert pos == T_long
         return sequence_stage(full, dvec.unsqueeze(0).contiguous())[0]
+
+
+def plan_ragged_batches(lengths, max_items: int, max_frames: int) -> List[List[int]]:
+    """Batches for ``model.forward_ragged`` over clips of unequal length: lists of indices into ``lengths`` such that every
+    index appears exactly once, no batch holds more than ``max_items`` clips and ``len(batch) * max(length in batch)`` -- the
+    frames the padded batch occupies -- stays within ``max_frames``.  Clips are sorted by length (longest first, ties by index)
+    and batches filled greedily, so batch mates differ little in length and few frames are padding.  A single clip longer
+    than ``max_frames`` still gets a batch of its own.  Pure host arithmetic, deterministic."""
+    if max_items < 1 or max_frames < 1:
+        raise ValueError(f"plan_ragged_batches: max_items = {max_items} and max_frames = {max_frames} must be positive")
+    lens = [int(n) for n in lengths]
+    if any(n < 1 for n in lens):
+        raise ValueError("plan_ragged_batches: every length must be at least 1")
+    order = sorted(range(len(lens)), key=lambda i: (-lens[i], i))
+    batches: List[List[int]] = []
+    for i in order:
+        cur = batches[-1] if batches else None
+        # longest first: the batch's first clip is its Tmax, so one more clip costs exactly that many frames
+        if cur is not None and len(cur) < max_items and (len(cur) + 1) * lens[cur[0]] <= max_frames:
+            cur.append(i)
+        else:
+            batches.append([i])
+    return batches
+
+
+def padded_frame_share(lengths, batches) -> float:
+    """Share of the frames of a plan's padded batches that is padding (0 = all clips of a batch share a length)."""
+    lens = [int(n) for n in lengths]
+    total = sum(len(b) * max(lens[i] for i in b) for b in batches)
+    return 1.0 - sum(lens) / total if total else 0.0

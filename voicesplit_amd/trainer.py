@@ -425,6 +425,42 @@ class Trainer:
         mean_sdr = acc[2] / acc[3] if acc[3] > 0 else float("nan")
         return mean_loss, mean_sdr
 
+    @torch.no_grad()
+    def evaluate_ragged(self, batches: Iterable):
+        """``evaluate`` for test items of unequal length, which the reference scores sample by sample at B = 1
+        (utils/generic_utils.py:476-530 under test.py's loader): the network runs on padded batches through
+        ``model.forward_ragged``, loss and SDR are computed PER ITEM at the item's own length and averaged over items -- the
+        B = 1 ``validation(test=True)`` semantics.  Batches are ``evaluate.eval_batches(..., ragged=True)``'s tuples
+        (emb, target, mixed, seq_len, target_wavs, phase, frames): spectrograms zero padded to the batch's longest item,
+        target_wavs a list of 1-D host waveforms, frames the items' own frame counts."""
+        from . import audio, metrics
+        self.model.eval()
+        acfg = self.c.audio[self.c.audio["backend"]]
+        dev = self.device
+        tot, cnt = 0.0, 0
+        sdr_acc = torch.zeros(2, dtype=torch.float64, device=dev)
+        for emb, target, mixed, seq_len, target_wavs, phase, frames in batches:
+            if emb is None or len(emb) == 0:
+                continue
+            emb, target, mixed, phase = (t.to(dev) for t in (emb, target, mixed, phase))
+            seq_len = seq_len.to(dev).reshape(-1)
+            mask = self.model.forward_ragged(mixed, emb, frames)
+            for b, n in enumerate(int(f) for f in frames):
+                item = [t[b:b + 1, :n] for t in (mask, mixed, target, phase)]      # leading rows of one item: contiguous views
+                tot += float(self.criterion(item[0], item[1], item[2], seq_len[b:b + 1], item[3]).item())
+                cnt += 1
+                est_wav = audio.spec_to_wav(item[1], item[3], acfg, mask=item[0])
+                sdr, status = metrics.bss_sdr(target_wavs[b].to(dev, torch.float32).reshape(1, -1), est_wav)
+                ok = status == 0
+                sdr_acc += torch.stack([torch.where(ok, sdr, torch.zeros_like(sdr)).sum(), ok.sum().to(torch.float64)])
+        acc = torch.cat([torch.tensor([tot, float(cnt)], dtype=torch.float64, device=dev), sdr_acc])
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(acc, group=self.group)
+        self.model.train()
+        acc = acc.tolist()
+        return (acc[0] / acc[1] if acc[1] > 0 else float("nan")), (acc[2] / acc[3] if acc[3] > 0 else float("nan"))
+
     def _with_decisions(self, batches: Iterable):
         """Yields (batch, have, next_missing) for ``train_step``.  One rank: have = None (decided in the step, no collective).
         Several ranks: the epoch's first two decisions come from ONE blocking MIN-reduce; from then on every rank's "my batch k + 2 is
