@@ -213,6 +213,37 @@ int vs_bilstm_fwd_ragged(const vs_dims* dims, const vs_params* params, const flo
 /* ptr [B][T] rows of row_bytes bytes each (a multiple of 4; ptr 16-byte aligned): rows t >= lengths[b] of item b := 0 */
 int vs_zero_tail_rows(void* ptr, int B, int T, size_t row_bytes, const int* lengths, void* stream);
 
+/* ---- eval-mode forward for K enrolled speakers per mixture with ONE conv pass ---------------------------------
+ * models/voicesplit/model.py:70-81 concatenates the d-vector to the conv features only at the LSTM input, so for K
+ * d-vectors of one mixture cnn1..cnn8 and the [B*T, 8F] x [8F, 8H] input GEMM are the same work K times over; only the
+ * recurrence and the head depend on the speaker.  x [B][T][F], dvecs [B][K][E] (any norm) -> mask [B][K][T][FC2]; row
+ * [b][k] is what vs_forward_prepared gives for x[b] with dvecs[b][k] (same kernels for the conv stack, the GEMM and the
+ * head; not bit-identical: the row bias is added by the recurrence, not by the GEMM's epilogue).
+ *   conv stack: once, for B; with lengths exactly as vs_forward_prepared_ragged runs it;
+ *   input GEMM: once, WITHOUT row bias, into G [B][T][8H] (the workspace's gate pre-activation region);
+ *   row biases: rb [B*K][8H] = dvecs @ W_ih[:, 8F:]^T + b_ih + b_hh, one small GEMM with M = B*K;
+ *   BiLSTM: the tagged persistent recurrence over the N = B*K sequences n = b*K + k in its shared-input mode: the columns
+ *     of a 32-column batch tile that belong to mixture b read the SAME row of G, each adds its own 16 values per lane of rb
+ *     (held in registers for the whole sequence) in fp32 before the gate functions; same grid, hand-off, bounded spins and
+ *     error word as the plain recurrence, launches of cus / (2*H/8) batch tiles;
+ *   head: over the B*K*T rows.
+ * lengths: NULL, or a DEVICE array [B] as in vs_forward_prepared_ragged -- per MIXTURE: every speaker k of mixture b is
+ * computed on x[b, :lengths[b]] alone, mask rows t >= lengths[b] are exactly 0 for every k, and what x holds behind an item's
+ * end changes no bit.
+ * Eval mode only, no tape.  Refused with an error code and a message, never computed some other way: VS_MATH_FP32, a
+ * recurrence other than the tagged persistent kernel (H > 448, vs_set_lstm_kernel not 0 or 2, a grid that is not resident),
+ * K < 1, NULL dvecs.
+ * workspace: vs_multi_workspace_bytes(dims, K) = vs_workspace_bytes(dims) (conv buffers, features and G for B -- NOT for B*K)
+ * + row biases, recurrence state, LSTM output and fc1 scratch for B*K sequences; 256-byte aligned. */
+size_t vs_multi_workspace_bytes(const vs_dims* dims, int K);
+int vs_forward_prepared_multi(const vs_dims* dims, const vs_params* params, const void* prepared, size_t prepared_bytes,
+                              const float* x, const float* dvecs, int K, const int* lengths_or_null, int conv_act,
+                              void* workspace, size_t workspace_bytes, float* mask, void* stream);
+/* the sequence stage of it: feat [B][T][8F] (vs_conv_stack_fwd / _ragged) -> lstm_out [B][K][T][2H] (rows t >= lengths[b]: 0);
+ * weights derived per call, as in the stage calls above; the head is vs_head_fwd over dims with B := B*K */
+int vs_bilstm_fwd_multi(const vs_dims* dims, const vs_params* params, const float* feat, const float* dvecs, int K,
+                        const int* lengths_or_null, void* workspace, size_t workspace_bytes, float* lstm_out, void* stream);
+
 /* ---- kernels (unit-test surface) --------------------------------------------------------- */
 /* BN(conv+bias) = conv*scale + shift */
 int vs_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,

@@ -83,6 +83,51 @@ def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg) -> torch.T
     return spec_to_wav(spec, phase, audio_cfg, mask=mask)
 
 
+def _multi_shapes(wav_shape, dvecs_shape):
+    """(B, n, K) of ``separate_speakers`` after the shape checks that need no device."""
+    if len(wav_shape) != 2:
+        raise ValueError(f"wav must be [B, n], got {tuple(wav_shape)}")
+    if len(dvecs_shape) != 3 or dvecs_shape[0] != wav_shape[0] or dvecs_shape[1] < 1:
+        raise ValueError(f"dvecs must be [B={wav_shape[0]}, K >= 1, emb_dim], got {tuple(dvecs_shape)}")
+    return int(wav_shape[0]), int(wav_shape[1]), int(dvecs_shape[1])
+
+
+def separate_speakers(model, wav: torch.Tensor, dvecs: torch.Tensor, audio_cfg) -> torch.Tensor:
+    """K enrolled speakers out of every mixture: wav [B, hop*(T-1)], dvecs [B, K, emb_dim] -> est_wav [B, K, hop*(T-1)]; row [b, k]
+    is ``separate(model, wav[b:b+1], dvecs[b:b+1, k])``.  One STFT, one ``model.forward_multi`` (one conv pass), one iSTFT over
+    the B*K rows with the mixture's spectrogram and phase repeated."""
+    B, n, K = _multi_shapes(wav.shape, dvecs.shape)
+    spec, phase = wav_to_spec(wav, audio_cfg)
+    with torch.no_grad():
+        masks = model.forward_multi(spec, dvecs)
+    T, F = spec.shape[1], spec.shape[2]
+    if tuple(masks.shape) != (B, K, T, F):
+        raise ValueError(f"forward_multi returned {tuple(masks.shape)}, expected {(B, K, T, F)}")
+
+    def per_speaker(t):          # [B, T, F] -> [B*K, T, F], row b*K + k = mixture b
+        return t[:, None].expand(B, K, T, F).reshape(B * K, T, F).contiguous()
+
+    est = spec_to_wav(per_speaker(spec), per_speaker(phase), audio_cfg, mask=masks.reshape(B * K, T, F).contiguous())
+    return est.view(B, K, n)
+
+
+def separate_speakers_with_reference(model, encoder, wav: torch.Tensor, ref_wavs, audio_cfg) -> torch.Tensor:
+    """``separate_speakers`` with the d-vectors computed here: ref_wavs[b] = a list of K reference waveforms (1-D, the same K for
+    every mixture; lengths as in ``separate_with_reference``), embedded in one ``encoder.embed_many`` call."""
+    from .speaker import logmel
+    if len(ref_wavs) != wav.shape[0]:
+        raise ValueError(f"{len(ref_wavs)} lists of reference waveforms for {wav.shape[0]} mixtures")
+    K = len(ref_wavs[0]) if len(ref_wavs) else 0
+    if K < 1 or any(len(r) != K for r in ref_wavs):
+        raise ValueError(f"every mixture needs the same number K >= 1 of reference waveforms, got {[len(r) for r in ref_wavs]}")
+    flat = [r for refs in ref_wavs for r in refs]
+    dvec, valid = encoder.embed_many([logmel(r, audio_cfg, encoder.num_mels) for r in flat])
+    if not bool(valid.all()):
+        short = [(i // K, i % K) for i, v in enumerate(valid.tolist()) if not v]
+        raise ValueError(f"reference waveforms {short} (mixture, speaker) are shorter than one encoder window of {encoder.window} frames")
+    return separate_speakers(model, wav, dvec.view(wav.shape[0], K, -1).contiguous(), audio_cfg)
+
+
 # frames a ragged batch may occupy (items * longest item): 64 clips of 3 s, the batch the workspace of the 3 s path is sized for anyway
 RAGGED_MAX_ITEMS = 64
 RAGGED_MAX_FRAMES = 64 * 301

@@ -155,9 +155,12 @@ int prep_pointers(const vs_dims* d, const void* blob, size_t bytes, Prep* P) {
 int conv_stack_impl(const vs_dims* d, const vs_params* p, const float* x, int conv_act, int bn_mode,
                     void* ws, const vs_ws_layout& L, float* feat, hipStream_t stream, const Prep* prep, bool* feat_rows = nullptr,
                     const int* lengths = nullptr /* device [B]: the ragged eval forward, see vs_forward_prepared_ragged */);
+// Several enrolled speakers per mixture (vs_bilstm_fwd_multi): dvec is [B][K][E]; the row biases and the recurrence's state are sized
+// for the B*K sequences and live behind the B-sized workspace (multi_layout), lstm_out is [B][K][T][2H]
+struct MultiBufs { int K; float* rb; float* lstm_state; };
 int bilstm_impl(const vs_dims* d, const vs_params* p, const float* feat, const float* dvec,
                 void* ws, const vs_ws_layout& L, float* lstm_out, hipStream_t stream, const Prep* prep, bool feat_rows = false,
-                const int* lengths = nullptr);
+                const int* lengths = nullptr, const MultiBufs* multi = nullptr);
 
 }  // namespace
 
@@ -855,12 +858,15 @@ int vs_bilstm_fwd(const vs_dims* d, const vs_params* p, const float* feat, const
 
 namespace {
 int bilstm_impl(const vs_dims* d, const vs_params* p, const float* feat, const float* dvec,
-                void* ws, const vs_ws_layout& L, float* lstm_out, hipStream_t stream, const Prep* prep, bool feat_rows, const int* lengths) {
+                void* ws, const vs_ws_layout& L, float* lstm_out, hipStream_t stream, const Prep* prep, bool feat_rows, const int* lengths,
+                const MultiBufs* multi) {
   VS_REQUIRE(p && dvec, "bilstm: NULL argument");
+  VS_REQUIRE(!multi || lstm_out, "bilstm: the multi-speaker form writes the caller's lstm_out");
   if (!feat) feat = at<float>(ws, L.feat);
   if (!lstm_out) lstm_out = at<float>(ws, L.lstm_out);
   const int B = d->B, T = d->T, H = d->H, K = 8 * d->F, KE = K + d->E;
-  float* dvbias = at<float>(ws, L.dvbias);
+  const int NS = multi ? B * multi->K : B;          // sequences of the recurrence = rows of the d-vector GEMM
+  float* dvbias = multi ? multi->rb : at<float>(ws, L.dvbias);
   float* xg = at<float>(ws, L.xg);
   {
   ProfScope ps(VS_PROF_LSTM_GEMM, stream);
@@ -868,14 +874,16 @@ int bilstm_impl(const vs_dims* d, const vs_params* p, const float* feat, const f
     VS_REQUIRE(p->w_ih[dir] && p->w_hh[dir] && p->b_ih[dir] && p->b_hh[dir], "bilstm: NULL LSTM parameter (dir %d)", dir);
     // cat((x, dvec.repeat(T))) @ W_ih^T == x @ W_ih[:, :8F]^T + (dvec @ W_ih[:, 8F:]^T): the
     // second term does not depend on t -> one [B][4H] row bias per utterance (+ b_ih + b_hh).
-    if (int rc = vs_gemm_nt_impl(dvec, d->E, p->w_ih[dir] + K, KE, dvbias + (size_t)dir * 4 * H, 8 * H, B, 4 * H, d->E,
+    if (int rc = vs_gemm_nt_impl(dvec, d->E, p->w_ih[dir] + K, KE, dvbias + (size_t)dir * 4 * H, 8 * H, NS, 4 * H, d->E,
                                  p->b_ih[dir], p->b_hh[dir], nullptr, 0, 1, 0, VS_ACT_NONE, stream)) return rc;
   }
+  // multi: the K speakers of a mixture share its gate pre-activations, so the big GEMM runs once per mixture WITHOUT the row bias;
+  // the shared-input recurrence adds each sequence's own (lstm.hip)
   // both directions in one launch (N = 8H): twice the workgroups, half the tail quantisation
   // the conv stack is done: its activation ping-pong is idle (feat may be the caller's own buffer)
   const size_t act_bytes = (size_t)B * 64 * T * d->F * sizeof(float);
   // feat_rows: cnn8 left the split A operand in the second ping-pong buffer (conv_stack_impl)
-  if (int rc = vs_lstm_input_gemm_impl(d->math, feat, K, p->w_ih[0], p->w_ih[1], H, KE, xg, B * T, dvbias, T,
+  if (int rc = vs_lstm_input_gemm_impl(d->math, feat, K, p->w_ih[0], p->w_ih[1], H, KE, xg, B * T, multi ? nullptr : dvbias, T,
                                        at<float>(ws, L.gemm_scales), at<char>(ws, feat_rows ? L.act1 : L.act0),
                                        feat_rows ? act_bytes : (L.act1 == L.act0 + act_bytes ? 2 * act_bytes : act_bytes), stream,
                                        prep ? prep->gemm_wscale : nullptr, prep ? prep->wih_hi : nullptr,
@@ -886,6 +894,8 @@ int bilstm_impl(const vs_dims* d, const vs_params* p, const float* feat, const f
   if (!prep) { if (int rc = vs_lstm_pack_impl(p->w_hh[0], p->w_hh[1], packed, H, stream, d->math)) return rc; }
   ProfScope ps(VS_PROF_LSTM_REC, stream);
   // (lengths: the input GEMM above ran over all B*T rows; the recurrence keeps the rows behind an item's end out of its state)
+  if (multi)
+    return vs_bilstm_recurrent_impl(xg, packed, multi->lstm_state, lstm_out, nullptr, nullptr, NS, T, H, stream, d->math, lengths, dvbias, multi->K);
   return vs_bilstm_recurrent_impl(xg, packed, at<float>(ws, L.lstm_state), lstm_out, nullptr, nullptr, B, T, H, stream, d->math, lengths);
 }
 }  // namespace
@@ -895,15 +905,12 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 // stage 3: head, models/voicesplit/model.py:83-87
 // ---------------------------------------------------------------------------------------------
-static int head_fwd_impl(const vs_dims* d, const vs_params* p, const float* lstm_out, void* ws, size_t ws_bytes,
-                         float* logits, float* mask, hipStream_t stream, const void* head_packed) {
-  vs_ws_layout L;
-  if (int rc = check_ws(d, ws, ws_bytes, &L)) return rc;
+// M rows of lstm_out [M][2H]; h1: [M][FC1] scratch; pack_scratch (pack_bytes): an idle buffer for the fused head's weight images
+// when they do not arrive prepared
+static int head_rows_impl(const vs_dims* d, const vs_params* p, const float* lstm_out, float* h1, int M, void* pack_scratch, size_t pack_bytes,
+                          float* logits, float* mask, hipStream_t stream, const void* head_packed) {
   VS_REQUIRE(p && p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b, "head: NULL parameter");
   VS_REQUIRE(mask || logits, "head: no output requested");
-  if (!lstm_out) lstm_out = at<float>(ws, L.lstm_out);
-  float* h1 = at<float>(ws, L.fc1_out);
-  const int M = d->B * d->T;
   ProfScope ps(VS_PROF_HEAD, stream);
   if (d->math == VS_MATH_BF16 && vs_head_fused_supported(2 * d->H, d->FC1, d->FC2)) {
     // one launch, h1 in registers between the two contractions (head_fused.hip).  The weights' fragment images come prepared
@@ -912,8 +919,8 @@ static int head_fwd_impl(const vs_dims* d, const vs_params* p, const float* lstm
     // the two-launch form below (same roundings, fp32 summation order differs)
     const size_t need = vs_head_fused_packed_bytes(2 * d->H, d->FC1, d->FC2);
     const void* img = head_packed;
-    if (!img && L.act1 - L.act0 >= need) {
-      void* scratch = at<void>(ws, L.act0);
+    if (!img && pack_scratch && pack_bytes >= need) {
+      void* scratch = pack_scratch;
       if (int rc = vs_head_fused_pack_impl(p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, 2 * d->H, d->FC1, d->FC2, scratch, stream)) return rc;
       img = scratch;
     }
@@ -934,6 +941,15 @@ static int head_fwd_impl(const vs_dims* d, const vs_params* p, const float* lstm
                                  p->fc2_b, nullptr, nullptr, 0, 1, 0, VS_ACT_SIGMOID, stream)) return rc;
   }
   return 0;
+}
+
+static int head_fwd_impl(const vs_dims* d, const vs_params* p, const float* lstm_out, void* ws, size_t ws_bytes,
+                         float* logits, float* mask, hipStream_t stream, const void* head_packed) {
+  vs_ws_layout L;
+  if (int rc = check_ws(d, ws, ws_bytes, &L)) return rc;
+  if (!lstm_out) lstm_out = at<float>(ws, L.lstm_out);
+  return head_rows_impl(d, p, lstm_out, at<float>(ws, L.fc1_out), d->B * d->T, at<void>(ws, L.act0), L.act1 - L.act0, logits, mask, stream,
+                        head_packed);
 }
 
 int vs_head_fwd(const vs_dims* d, const vs_params* p, const float* lstm_out, void* ws, size_t ws_bytes,
@@ -1063,6 +1079,90 @@ int vs_bilstm_fwd_ragged(const vs_dims* d, const vs_params* p, const float* feat
 
 int vs_zero_tail_rows(void* ptr, int B, int T, size_t row_bytes, const int* lengths, void* stream) {
   return vs_zero_tail_rows_impl(ptr, B, T, row_bytes, lengths, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// several enrolled speakers per mixture: conv stack and LSTM input GEMM once, recurrence and head per speaker (see the header)
+// ---------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+// the workspace of vs_workspace_bytes(dims) -- conv buffers, features and the shared gate pre-activations G = its xg region, all for B --
+// followed by what grows with the B*K sequences
+struct MultiLayout { vs_ws_layout base; size_t rb, lstm_state, lstm_out, fc1_out, total_bytes; };
+
+int multi_layout(const vs_dims* d, int K, MultiLayout* M) {
+  if (int rc = layout(d, &M->base)) return rc;
+  VS_REQUIRE(K >= 1, "multi: K=%d speakers per mixture (K >= 1)", K);
+  VS_REQUIRE((long long)d->B * K * d->T < 2147483647LL / 8 && (long long)d->B * K <= 65535, "multi: B*K*T too large (B=%d K=%d T=%d)", d->B, K, d->T);
+  const size_t N = (size_t)d->B * K, T = d->T, H = d->H;
+  size_t off = align_up(M->base.total_bytes);
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
+  M->rb = take(N * 8 * H * 4);
+  M->lstm_state = take(vs_lstm_state_floats((int)N, d->H) * 4);
+  M->lstm_out = take(N * T * 2 * H * 4);
+  M->fc1_out = take(N * T * (size_t)d->FC1 * 4);
+  M->total_bytes = off;
+  return 0;
+}
+
+int check_multi(const vs_dims* d, const float* dvecs, int K, const char* what) {
+  if (int rc = check_dims(d)) return rc;
+  VS_REQUIRE(K >= 1, "%s: K=%d speakers per mixture (K >= 1)", what, K);
+  VS_REQUIRE(dvecs != nullptr, "%s: dvecs is NULL", what);
+  VS_REQUIRE(d->math == VS_MATH_F16X3 || d->math == VS_MATH_BF16,
+             "%s: several speakers per mixture are served by VS_MATH_F16X3 and VS_MATH_BF16; VS_MATH_FP32 has no shared-input recurrence", what);
+  return 0;
+}
+
+int check_multi_ws(const vs_dims* d, int K, void* ws, size_t ws_bytes, MultiLayout* M) {
+  if (int rc = multi_layout(d, K, M)) return rc;
+  VS_REQUIRE(ws != nullptr, "workspace is NULL");
+  VS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
+  VS_REQUIRE(ws_bytes >= M->total_bytes, "workspace too small: %zu < %zu bytes (vs_multi_workspace_bytes)", ws_bytes, M->total_bytes);
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+size_t vs_multi_workspace_bytes(const vs_dims* dims, int K) {
+  MultiLayout M;
+  memset(&M, 0, sizeof(M));
+  if (multi_layout(dims, K, &M)) return 0;
+  return M.total_bytes;
+}
+
+int vs_bilstm_fwd_multi(const vs_dims* d, const vs_params* p, const float* feat, const float* dvecs, int K, const int* lengths,
+                        void* ws, size_t ws_bytes, float* lstm_out, void* stream_) {
+  if (int rc = check_multi(d, dvecs, K, "bilstm_fwd_multi")) return rc;
+  VS_REQUIRE(feat && lstm_out, "bilstm_fwd_multi: NULL argument");
+  MultiLayout M;
+  if (int rc = check_multi_ws(d, K, ws, ws_bytes, &M)) return rc;
+  const MultiBufs mb{K, at<float>(ws, M.rb), at<float>(ws, M.lstm_state)};
+  return bilstm_impl(d, p, feat, dvecs, ws, M.base, lstm_out, (hipStream_t)stream_, nullptr, false, lengths, &mb);
+}
+
+int vs_forward_prepared_multi(const vs_dims* d, const vs_params* p, const void* prepared, size_t prepared_bytes,
+                              const float* x, const float* dvecs, int K, const int* lengths, int conv_act,
+                              void* ws, size_t ws_bytes, float* mask, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (int rc = check_multi(d, dvecs, K, "forward_prepared_multi")) return rc;
+  VS_REQUIRE(mask != nullptr, "forward_prepared_multi: mask is NULL");
+  Prep P;
+  if (int rc = prep_pointers(d, prepared, prepared_bytes, &P)) return rc;
+  MultiLayout M;
+  if (int rc = check_multi_ws(d, K, ws, ws_bytes, &M)) return rc;
+  bool feat_rows = false;
+  if (int rc = conv_stack_impl(d, p, x, conv_act, VS_BN_EVAL, ws, M.base, nullptr, stream, &P, &feat_rows, lengths)) return rc;
+  const MultiBufs mb{K, at<float>(ws, M.rb), at<float>(ws, M.lstm_state)};
+  float* lstm_out = at<float>(ws, M.lstm_out);
+  if (int rc = bilstm_impl(d, p, nullptr, dvecs, ws, M.base, lstm_out, stream, &P, feat_rows, lengths, &mb)) return rc;
+  // the head over the B*K*T rows; the conv stack's first activation buffer is idle by now (the fused head's weight images, when not prepared)
+  if (int rc = head_rows_impl(d, p, lstm_out, at<float>(ws, M.fc1_out), d->B * K * d->T, at<void>(ws, M.base.act0), M.base.act1 - M.base.act0,
+                              nullptr, mask, stream, P.head_packed)) return rc;
+  if (!lengths) return 0;
+  return vs_zero_tail_rows_impl(mask, d->B * K, d->T, sizeof(float) * (size_t)d->FC2, lengths, stream, K);
 }
 
 // ---------------------------------------------------------------------------------------------

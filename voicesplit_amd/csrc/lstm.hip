@@ -1004,9 +1004,22 @@ constexpr unsigned kSentinel = 0x7FFF7FFFu;
 // h = c = 0 while t >= lengths[b] -- two selects per gate lane, the same schedule and hand-off.  The reverse direction then reaches
 // t = lengths[b] - 1 with the zero state of a fresh clip, the forward direction writes zeros past the end.  Selects, not products:
 // whatever xg holds in those rows (NaN included) stays out.  !RAGGED is the kernel as it was (lengths unused).
-template <int NP, bool RAGGED>
+//
+// SHARED (several enrolled speakers per mixture, vs_bilstm_fwd_multi): the launch runs N = a.B sequences n = m*K + k, speaker k of
+// mixture m.  The d-vector enters the gates only as a row bias that does not depend on t, so the K sequences of a mixture share ONE
+// row of gate pre-activations: wave 0 reads xg [N / K][T][8H] (the input GEMM run once, WITHOUT row bias) at mixture n / K -- columns
+// of a tile that belong to one mixture read the same row -- and adds the lane's 16 values of sh.rowbias [N][8H], loaded once in front of
+// the time loop and held in registers, in fp32 before the gate functions.  lengths (RAGGED) are per mixture: lengths[n / K].  Padding
+// columns n >= N behave as b >= B does.  Schedule, hand-off, spins and error word are the kernel's own; !SHARED is the kernel as it
+// was (sh unused).
+struct LstmSharedIn {
+  const float* rowbias;   // [N][8H]: dvec @ W_ih[:, 8F:]^T + b_ih + b_hh of sequence n, both directions
+  int K;                  // sequences per shared row of xg
+};
+
+template <int NP, bool RAGGED, bool SHARED = false>
 __global__ __launch_bounds__(256)
-void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __restrict__ lengths) {
+void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __restrict__ lengths, LstmSharedIn sh) {
   __shared__ float sRed[2][3 * 16 * 64];      // by step parity: no barrier separates wave 0's reads of step s from the other waves' writes of step s + 1
   __shared__ int sDead;
   const int tid = threadIdx.x;
@@ -1045,8 +1058,16 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __r
   const unsigned slot_off = (unsigned)((((group * NC + (jg >> 1)) * NP + plane) * 64 + (jg & 1) * 32 + l31) * 16);
   const bool storer = NP == 2 || half == 0;
   float cprev[4] = {0.f, 0.f, 0.f, 0.f};
+  const int xb = SHARED ? b / sh.K : b;          // the row of xg (and of lengths) this column reads
   int len = a.T;
-  if (RAGGED) len = b < a.B ? lengths[b] : 0;
+  if (RAGGED) len = b < a.B ? lengths[xb] : 0;
+  float rbv[16];                                 // SHARED: this lane's row bias, resident for the whole sequence (wave 0)
+  if (SHARED && wave == 0) {
+    const bool ok = b < a.B;
+    const float* rrow = sh.rowbias + (size_t)(ok ? b : 0) * (8 * a.H) + (size_t)dir * 4 * a.H + jg * 8 + 4 * half;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rbv[r] = ok ? rrow[(r >> 2) * a.H + (r & 3)] : 0.f;
+  }
   __syncthreads();
 
 #pragma unroll 1
@@ -1056,7 +1077,7 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __r
     float xgv[16];
     if (wave == 0) {
       const bool ok = b < a.B;
-      const float* xrow = a.xg + ((size_t)(ok ? b : 0) * a.T + t) * (8 * a.H) + (size_t)dir * 4 * a.H + jg * 8 + 4 * half;
+      const float* xrow = a.xg + ((size_t)(ok ? xb : 0) * a.T + t) * (8 * a.H) + (size_t)dir * 4 * a.H + jg * 8 + 4 * half;
 #pragma unroll
       for (int r = 0; r < 16; ++r) xgv[r] = ok ? xrow[(r >> 2) * a.H + (r & 3)] : 0.f;
     }
@@ -1115,6 +1136,10 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __r
       for (int w3 = 0; w3 < 3; ++w3)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] += sRed[s & 1][(w3 * 16 + r) * 64 + lane];
+      if (SHARED) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) xgv[r] += rbv[r];
+      }
       float hv[4], cnew[4], gact[4][4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -1418,9 +1443,12 @@ hipError_t launch_resident(const void* kernel, dim3 grid, dim3 block, Args& a, h
 
 // state: 3 * [2][H][Bpad] floats.  Step kernels: h ping, h pong, c, zeroed here (zero initial state).
 // Persistent kernel: h ping, h pong (fragment order), then the flag words + the error word.
+// rowbias != NULL: the shared-input form (lstm16_tagged_kernel<.., SHARED>): B sequences n = m*K + k read xg [B / K][T][8H] at mixture
+// n / K and add rowbias [B][8H]; lengths, when given, are per mixture [B / K]; out [B][T][2H]
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
-                             int B, int T, int H, hipStream_t stream, int math, const int* lengths) {
+                             int B, int T, int H, hipStream_t stream, int math, const int* lengths, const float* rowbias, int K) {
   VS_REQUIRE(B > 0 && T > 0 && H > 0 && H % 8 == 0, "lstm: bad shape B=%d T=%d H=%d (H must be a multiple of 8)", B, T, H);
+  VS_REQUIRE(rowbias ? (K >= 1 && B % K == 0) : K == 1, "lstm: %d sequences do not share rows of xg in groups of K=%d", B, K);
   const int Bpad = (B + 31) / 32 * 32;
   const size_t per = lstm_state_region(B, H);
   if (g_lstm_kernel == 3) math = VS_MATH_CODE_FP32;
@@ -1441,6 +1469,10 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
   VS_REQUIRE(!lengths || (tagged && !gates_save && !c_save),
              "lstm: per-item lengths need the tagged persistent recurrence in eval mode (dims.math F16X3 or BF16, H <= %d, 2*H/8 = %d workgroups "
              "<= %d CUs, vs_set_lstm_kernel 0 or 2); VS_MATH_FP32, the flag kernel and the per-step kernels do not take them", 64 * kMaxC, 2 * HQ, cus);
+  VS_REQUIRE(!rowbias || (tagged && !gates_save && !c_save),
+             "lstm: the shared-input recurrence (several speakers per mixture) is the tagged persistent recurrence in eval mode (dims.math F16X3 or "
+             "BF16, H <= %d, 2*H/8 = %d workgroups <= %d CUs, vs_set_lstm_kernel 0 or 2); VS_MATH_FP32, the flag kernel and the per-step kernels "
+             "do not offer it", 64 * kMaxC, 2 * HQ, cus);
   if (tagged) VS_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(state + per), (int)kSentinel, 3 * per, stream));
   if (persistent) {
     unsigned* flags = reinterpret_cast<unsigned*>(state + 2 * per);      // zeroed above
@@ -1460,10 +1492,15 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
         if (tagged) {
           void* hb2 = state + 2 * per;
           void* hb3 = state + 3 * per;
-          void* params[] = {&a, &hb2, &hb3, &lengths};
+          LstmSharedIn sh{rowbias, K};
+          void* params[] = {&a, &hb2, &hb3, &lengths, &sh};
           const void* kernel = math == VS_MATH_CODE_BF16
               ? (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, false>))
               : (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, false>));
+          if (rowbias)
+            kernel = math == VS_MATH_CODE_BF16
+                ? (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, true, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, false, true>))
+                : (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, true, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, false, true>));
           e = hipLaunchCooperativeKernel(kernel, dim3(HQ * nbt, 2), dim3(256), params, 0, stream);
         } else
         e = math == VS_MATH_CODE_BF16
@@ -1476,6 +1513,8 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
         VS_REQUIRE(bt0 == 0 && g_lstm_kernel != 2, "lstm: persistent recurrence could not be launched resident: %s", hipGetErrorString(e));
         VS_REQUIRE(!lengths, "lstm: per-item lengths: the persistent recurrence could not be launched resident (%s) and the per-step kernels do not take them",
                    hipGetErrorString(e));
+        VS_REQUIRE(!rowbias, "lstm: shared-input recurrence: the persistent recurrence could not be launched resident (%s) and the per-step kernels do not "
+                   "offer it", hipGetErrorString(e));
         launched = false;
         break;
       }

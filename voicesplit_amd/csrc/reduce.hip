@@ -65,9 +65,9 @@ constexpr int kZeroVecs = 4;                            // 16-byte stores per th
 constexpr long long kZeroChunk = 256 * kZeroVecs * 4;   // dwords per workgroup
 
 __global__ __launch_bounds__(256)
-void zero_tail_rows_kernel(unsigned* __restrict__ p, int T, long long row_words, const int* __restrict__ lengths) {
+void zero_tail_rows_kernel(unsigned* __restrict__ p, int T, long long row_words, const int* __restrict__ lengths, int share) {
   const int b = blockIdx.y;
-  int len = lengths[b];
+  int len = lengths[b / share];
   len = len < 0 ? 0 : (len > T ? T : len);
   const long long begin = ((long long)b * T + len) * row_words, end = (long long)(b + 1) * T * row_words;
   const long long body = (begin + 3) & ~3LL;            // first dword on a 16-byte boundary (p itself is aligned)
@@ -91,14 +91,15 @@ void zero_tail_rows_kernel(unsigned* __restrict__ p, int T, long long row_words,
 
 }  // namespace
 
-int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t stream) {
+int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t stream, int share) {
   VS_REQUIRE(ptr && lengths, "zero_tail_rows: NULL argument");
+  VS_REQUIRE(share >= 1, "zero_tail_rows: share=%d rows per length must be at least 1", share);
   VS_REQUIRE(B > 0 && B <= 65535 && T > 0 && row_bytes > 0 && row_bytes % 4 == 0, "zero_tail_rows: bad shape B=%d T=%d row_bytes=%zu", B, T, row_bytes);
   VS_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & 15) == 0, "zero_tail_rows: the array must be 16-byte aligned");
   const long long row_words = (long long)(row_bytes / 4);
   const long long nb = ((long long)T * row_words + kZeroChunk - 1) / kZeroChunk;
   VS_REQUIRE(nb < 2147483647LL, "zero_tail_rows: array too large");
-  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, stream, static_cast<unsigned*>(ptr), T, row_words, lengths);
+  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, stream, static_cast<unsigned*>(ptr), T, row_words, lengths, share);
   VS_LAUNCH_CHECK();
   return 0;
 }

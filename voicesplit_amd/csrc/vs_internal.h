@@ -253,7 +253,9 @@ inline VsLstmBf16Layout vs_lstm_bf16_layout(long long M, int K, int H) {
 int vs_lstm_pack_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
                              int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32,
-                             const int* lengths = nullptr /* device [B]: h = c = 0 while t >= lengths[b]; only the tagged persistent kernel takes them */);
+                             const int* lengths = nullptr /* device [B]: h = c = 0 while t >= lengths[b]; only the tagged persistent kernel takes them */,
+                             const float* rowbias = nullptr /* [B][8H]: the shared-input form, xg [B / K][T][8H] and lengths [B / K] (lstm.hip) */,
+                             int K = 1);
 int vs_lstm_pack_t_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
 int vs_bilstm_bwd_recurrent_impl(const float* wpt, float* state, float* gates, const float* c_all, const float* dout,
                                  int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32);
@@ -262,4 +264,5 @@ int vs_sigmoid_bwd_impl(const float* dmask, const float* mask, float* dlogits, l
 int vs_sigmoid_bwd_rows_impl(const float* dmask, const float* mask, float* dlogits, long long rows, int N, void* rows_bf16, int Kp, hipStream_t);
 int vs_colsum_impl(const float* x, int ld, int groups, int rows, int N, float* out, int ldo, hipStream_t);
 // rows t >= lengths[b] of a [B][T][row_bytes] array := 0 (the ragged eval forward: capi.hip)
-int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t);
+// (share > 1: item b ends at lengths[b / share] -- the K masks of one mixture)
+int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t, int share = 1);

@@ -271,6 +271,13 @@ class _MaskNet(nn.Module):
 
         def sequence_stage(feat, dvec):
             dims = self._dims(feat.shape[0], feat.shape[1])
+            if dvec.dim() == 3:
+                # [B, K, emb_dim]: K enrolled speakers per sequence -> [B, K, T, fc2_dim]; one input GEMM, the shared-input
+                # recurrence over the B*K sequences, the head over B*K*T rows
+                B, K = dvec.shape[0], dvec.shape[1]
+                lo = ops.bilstm_multi(sd, feat.contiguous(), dvec.contiguous(), dims)
+                flat = self._dims(B * K, feat.shape[1])
+                return ops.head(sd, lo.view(B * K, feat.shape[1], -1), flat).view(B, K, feat.shape[1], -1)
             return ops.head(sd, ops.bilstm(sd, feat.contiguous(), dvec.contiguous(), dims), dims)
 
         return conv_stage, sequence_stage
@@ -296,6 +303,29 @@ class _MaskNet(nn.Module):
             prep = ops.PreparedWeights(sd, dims)
             self.__dict__["_prepared"] = prep
         return ops.forward_prepared(sd, prep, x, dvec, dims, self.conv_act, lengths=lengths)
+
+    def forward_multi(self, x, speaker_embeddings, lengths=None):
+        """K enrolled speakers per mixture with ONE pass of the conv stack: x [B, T, num_freq], speaker_embeddings [B, K, emb_dim]
+        -> masks [B, K, T, fc2_dim]; row [b, k] is what ``self(x[b:b+1], speaker_embeddings[b:b+1, k])`` gives.  The d-vector reaches
+        the network only at the LSTM input (models/voicesplit/model.py:70-81), so the conv stack and the LSTM input GEMM run once
+        per mixture; the recurrence and the head run per speaker.  lengths (one per MIXTURE, as in ``forward_ragged``): a padded
+        batch of clips of unequal length, each as if alone; rows t >= lengths[b] are exactly 0 for every k.  Inference only: eval
+        mode, no autograd."""
+        if self.training:
+            raise RuntimeError("forward_multi runs in eval mode (BatchNorm running statistics, no tape): call model.eval() first")
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_multi produces no gradients: call it under torch.no_grad()")
+        if speaker_embeddings.dim() != 3 or speaker_embeddings.shape[0] != x.shape[0]:
+            raise ValueError(f"speaker_embeddings must be [B={x.shape[0]}, K, emb_dim], got {tuple(speaker_embeddings.shape)}")
+        x = x.contiguous()
+        dvecs = speaker_embeddings.contiguous()
+        dims = self._dims(x.shape[0], x.shape[1])
+        sd = self._tensors()
+        prep = self.__dict__.get("_prepared")
+        if prep is None or not prep.matches(sd, dims):
+            prep = ops.PreparedWeights(sd, dims)
+            self.__dict__["_prepared"] = prep
+        return ops.forward_prepared_multi(sd, prep, x, dvecs, dims, self.conv_act, lengths=lengths)
 
     def forward(self, x, speaker_embedding):
         # x: [B, T, num_freq]; speaker_embedding: [B, emb_dim]  ->  mask [B, T, fc2_dim]

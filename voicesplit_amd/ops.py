@@ -91,8 +91,29 @@ def get_workspace(dims: VsDims, device) -> torch.Tensor:
     return ws
 
 
+_MULTI_WS_CACHE: Dict[tuple, torch.Tensor] = {}
+
+
+def get_multi_workspace(dims: VsDims, K: int, device) -> torch.Tensor:
+    """Scratch of the multi-speaker calls (vs_multi_workspace_bytes: conv buffers for B, sequence buffers for B*K), cached on
+    (device, dims, K).  One buffer per device is kept: another shape replaces it (at B = 64 it holds gigabytes)."""
+    dev = torch.device(device).index
+    key = (dev, dims.B, dims.T, dims.F, dims.E, dims.H, dims.FC1, dims.FC2, dims.math, int(K))
+    ws = _MULTI_WS_CACHE.get(key)
+    if ws is None:
+        nbytes = _lib.load().vs_multi_workspace_bytes(ctypes.byref(dims), int(K))
+        if nbytes == 0:
+            check(-1, "vs_multi_workspace_bytes")
+        for k in [k for k in _MULTI_WS_CACHE if k[0] == dev]:
+            del _MULTI_WS_CACHE[k]            # drop the old buffer before allocating the next one
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _MULTI_WS_CACHE[key] = ws
+    return ws
+
+
 def release_workspaces():
     _WS_CACHE.clear()
+    _MULTI_WS_CACHE.clear()
     _TAPE_POOL.clear()
 
 
@@ -217,6 +238,56 @@ def forward_prepared(sd, prepared: PreparedWeights, x, dvec, dims: VsDims, conv_
                                      _p(x), _p(dvec), ACT_CODES[conv_act], _p(ws), ws.numel(), _p(mask), _stream())
     check(rc, "vs_forward_prepared")
     return mask
+
+
+def _check_multi_inputs(x, dvecs, dims: VsDims):
+    _dev_check(x, "x")
+    _dev_check(dvecs, "speaker_embeddings")
+    if x.dim() != 3 or x.shape[2] != dims.F:
+        raise ValueError(f"x must be [B, T, num_freq={dims.F}] (F contiguous), got {tuple(x.shape)}")
+    _check_multi_dvecs(dvecs, x.shape[0], dims)
+
+
+def _check_multi_dvecs(dvecs, B: int, dims: VsDims):
+    if dvecs.dim() != 3 or dvecs.shape[0] != B or dvecs.shape[1] < 1 or dvecs.shape[2] != dims.E:
+        raise ValueError(f"speaker_embeddings must be [B={B}, K >= 1, emb_dim={dims.E}], got {tuple(dvecs.shape)}")
+
+
+def forward_prepared_multi(sd, prepared: PreparedWeights, x, dvecs, dims: VsDims, conv_act: str,
+                           workspace: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
+    """Eval-mode masks [B, K, T, FC2] of K enrolled speakers per mixture (dvecs [B, K, E]) with one conv pass and one LSTM input
+    GEMM (vs_forward_prepared_multi); lengths as in ``forward_prepared``, one per mixture."""
+    lib = _lib.load()
+    _check_multi_inputs(x, dvecs, dims)
+    K = int(dvecs.shape[1])
+    params = pack_params(sd)
+    ws = workspace if workspace is not None else get_multi_workspace(dims, K, x.device)
+    lens = device_lengths(lengths, dims.B, dims.T, x.device) if lengths is not None else None
+    mask = torch.empty(dims.B, K, dims.T, dims.FC2, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.vs_forward_prepared_multi(ctypes.byref(dims), ctypes.byref(params), _p(prepared.buf), prepared.buf.numel(),
+                                           _p(x), _p(dvecs), K, _p(lens), ACT_CODES[conv_act], _p(ws), ws.numel(), _p(mask), _stream())
+    check(rc, "vs_forward_prepared_multi")
+    return mask
+
+
+def bilstm_multi(sd, feat, dvecs, dims: VsDims, lengths=None, workspace=None) -> torch.Tensor:
+    """feat [B, T, 8F], dvecs [B, K, E] -> LSTM output [B, K, T, 2H]: one input GEMM per mixture, the shared-input recurrence over
+    the B*K sequences (vs_bilstm_fwd_multi).  lengths (one per mixture): rows t >= lengths[b] are 0 for every k."""
+    lib = _lib.load()
+    _dev_check(feat, "feat")
+    _dev_check(dvecs, "speaker_embeddings")
+    _check_multi_dvecs(dvecs, feat.shape[0], dims)
+    K = int(dvecs.shape[1])
+    params = pack_params(sd)
+    ws = workspace if workspace is not None else get_multi_workspace(dims, K, feat.device)
+    lens = device_lengths(lengths, dims.B, dims.T, feat.device) if lengths is not None else None
+    out = torch.empty(dims.B, K, dims.T, 2 * dims.H, dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device):
+        rc = lib.vs_bilstm_fwd_multi(ctypes.byref(dims), ctypes.byref(params), _p(feat), _p(dvecs), K, _p(lens), _p(ws), ws.numel(),
+                                     _p(out), _stream())
+    check(rc, "vs_bilstm_fwd_multi")
+    return out
 
 
 def conv_stack(sd, x, dims: VsDims, conv_act: str, training: bool = False, workspace=None) -> torch.Tensor:
