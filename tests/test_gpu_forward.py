@@ -324,3 +324,62 @@ def test_cnn8_writing_the_gemm_operand_agrees_with_the_separate_passes(F, B, T, 
     ref = R.forward(R.cast_state_dict(sd, torch.float64), x.double(), dvec.double(), act="mish")["mask"]
     assert _rel(got[1].numpy(), ref.numpy()) < REL_TOL and _rel(got[0].numpy(), ref.numpy()) < REL_TOL
     assert _rel(got[1].numpy(), got[0].numpy()) < 2e-6
+
+
+_TRAIN_REF = {}
+
+
+def _train_mode_reference(B, T):
+    """Seeded inputs and the fp64 oracle's train-mode forward on them: mask and the sixteen running statistics after the call.
+    Computed once per shape and shared by the arithmetics; read only."""
+    if (B, T) not in _TRAIN_REF:
+        dims_d = dict(num_freq=53, emb_dim=24, lstm_dim=32, fc1_dim=44, fc2_dim=53)
+        sd = R.spread_logits(R.build_state_dict(dims_d, 21), 6.0)
+        x, dvec = R.synthetic_inputs(B, T, dims_d, 21)
+        bn_out = {}
+        with torch.no_grad():
+            ref = R.forward(R.cast_state_dict(sd, torch.float64), x.double(), dvec.double(), act="mish", training=True, bn_out=bn_out,
+                            lstm_impl="loop")
+        stats = {k: v.numpy() for k, v in bn_out.items() if "running_" in k}
+        assert len(stats) == 16
+        _TRAIN_REF[(B, T)] = (sd, x, dvec, ref["mask"].numpy(), stats)
+    return _TRAIN_REF[(B, T)]
+
+
+@pytest.mark.parametrize("math", ["fp32", "f16x3", "bf16"])
+@pytest.mark.parametrize("B,T", [(2, 45), (5, 17)])
+def test_tapeless_train_mode_forward_matches_fp64_oracle(B, T, math):
+    """model.train() under no_grad: vs_forward with batch-statistics BatchNorm and no tape, in every arithmetic (the bf16 one runs cnn1
+    by recomputation, the in-place BatchNorm apply and the feature-layout BatchNorm of cnn8).  Mask and the sixteen running statistics
+    after the call against the fp64 oracle.  Bounds: this file's for the fp32-class arithmetics; for bf16 the mask bounds that
+    tests/test_gpu_bf16.py holds the training=True forward of the same fixture to (max abs 6e-2, MSE 1e-4), and for its running
+    statistics the 2e-2 of tests/test_gpu_nhwc.py's train-mode conv stack (relative to the tensor's maximum, floor 1e-6)."""
+    import voicesplit_amd as V
+    from voicesplit_amd import ops
+    sd, x, dvec, ref_mask, ref_stats = _train_mode_reference(B, T)
+    prev = ops.get_conv_math()
+    ops.set_conv_math(math)
+    try:
+        m = V.VoiceSplit(V.default_config(53, 24, 32, 44, 53))
+        m.load_state_dict(sd, strict=True)
+        m = m.cuda().train()
+        with torch.no_grad():
+            mask = m(x.cuda(), dvec.cuda())
+        torch.cuda.synchronize()
+    finally:
+        ops.set_conv_math(prev)
+    mask = mask.double().cpu().numpy()
+    after = {k: v.double().cpu().numpy() for k, v in m.state_dict().items() if "running_" in k}
+    assert sorted(after) == sorted(ref_stats)
+    abs_err, mse = np.abs(mask - ref_mask).max(), ((mask - ref_mask) ** 2).mean()
+    stat_err = {k: np.abs(after[k] - ref_stats[k]).max() / max(np.abs(ref_stats[k]).max(), 1e-6 if math == "bf16" else 1e-30) for k in after}
+    print(f"tapeless train forward {math} B={B} T={T}: mask rel {_rel(mask, ref_mask):.3e} abs {abs_err:.3e} mse {mse:.3e}; "
+          f"worst running statistic {max(stat_err.values()):.3e}")
+    assert mask.shape == ref_mask.shape and np.isfinite(mask).all()
+    if math == "bf16":
+        assert abs_err < 6e-2 and mse < 1e-4
+        assert max(stat_err.values()) < 2e-2, stat_err
+    else:
+        assert _rel(mask, ref_mask) < REL_TOL and mse < MSE_TOL
+        assert max(stat_err.values()) < REL_TOL, stat_err
+    assert all(int(v) == 1 for k, v in m.state_dict().items() if "num_batches" in k)

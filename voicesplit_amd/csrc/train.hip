@@ -11,8 +11,6 @@
 #include "../../include/voicesplit_hip.h"
 #include "vs_internal.h"
 
-int vs_check_dims_impl(const vs_dims* d);   // capi.hip
-
 namespace {
 
 constexpr int kSplitK = 16;    // split-K factor of the small weight-gradient GEMMs (fc1, fc2, W_hh)
@@ -443,11 +441,12 @@ int lstm(const Step& st, const float* dvec, bool feat_bf16_ready) {
       for (int dir = 0; dir < 2; ++dir)
         if (int rc = dvec_bias(st, dvec, dir, st.stream)) return rc;
     }
-    const _Float16* wih_ready = st.nhwc ? reinterpret_cast<const _Float16*>(st.at<char>(L.lstm_bf16) + st.lb.wih) : nullptr;
+    VsLstmGemmReady ready;
+    ready.wh = st.nhwc ? reinterpret_cast<const _Float16*>(st.at<char>(L.lstm_bf16) + st.lb.wih) : nullptr;
+    ready.feat_bf16 = feat_bf16_ready;
     if (int rc = vs_lstm_input_gemm_impl(st.d->math, st.at<float>(L.feat), st.K8, p->w_ih[0], p->w_ih[1], st.H, st.KE, xg, st.M, st.at<float>(L.dvbias), st.T,
                                          st.at<float>(L.gemm_scales), st.nhwc ? st.at<char>(L.lstm_bf16) : st.at<char>(L.grad0),
-                                         st.nhwc ? L.total_bytes - L.lstm_bf16 : 2 * (L.grad1 - L.grad0), st.stream, nullptr, wih_ready, nullptr,
-                                         feat_bf16_ready)) return rc;
+                                         st.nhwc ? L.total_bytes - L.lstm_bf16 : 2 * (L.grad1 - L.grad0), st.stream, ready)) return rc;
   }
   if (!st.nhwc) {
     if (int rc = vs_lstm_pack_impl(p->w_hh[0], p->w_hh[1], packed, st.H, st.stream, st.d->math)) return rc;

@@ -1,6 +1,6 @@
-// Prototypes of the per-kernel host launchers shared by capi.hip (inference orchestration) and
-// train.hip (training forward + backward orchestration), and the small host helpers the
-// orchestration files share.  Internal to libvoicesplit_hip.so.
+// Prototypes of the per-kernel host launchers shared by forward.hip (inference orchestration),
+// train.hip (training forward + backward orchestration) and capi.hip (the kernel-level surface), and
+// the small host helpers the orchestration files share.  Internal to libvoicesplit_hip.so.
 #pragma once
 #include "vs_common.h"
 
@@ -24,7 +24,7 @@ struct VsTurnScope {
 };
 inline int vs_det_grid(int nb, int cus = 256) { return (g_vs_turn && nb > cus) ? cus : nb; }      // deterministic mode: at most one workgroup per CU takes turns
 
-// ---- host helpers shared by the orchestration files (capi.hip, train.hip, loss.hip, speaker.hip) ----
+// ---- host helpers shared by the orchestration files (forward.hip, train.hip, loss.hip, speaker.hip) ----
 constexpr float kBnEps = 1e-5f;       // nn.BatchNorm2d default (models/voicesplit/model.py:19)
 constexpr float kBnMomentum = 0.1f;
 // conv-stack table (models/voicesplit/model.py:15-52): KT, KF, time dilation
@@ -36,6 +36,7 @@ template <typename T>
 inline T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 template <typename T>
 inline const T* at(const void* base, size_t off) { return reinterpret_cast<const T*>(static_cast<const char*>(base) + off); }
+int vs_check_dims_impl(const vs_dims* d);   // forward.hip
 
 // conv_mfma.hip
 int vs_conv64_pack_impl(const float* w, float* wp, int KT, int KF, int transpose_flip, hipStream_t);
@@ -59,16 +60,32 @@ int vs_gemm_f16x3_impl(int layout_a, int layout_w, const float* A, int lda, cons
                        const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
                        const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
                        const float* a_scale2, const float* w_scale2, hipStream_t, int math = VS_MATH_CODE_F16X3);
+// The split-f16 operand arrays of the LSTM input GEMM inside one scratch region (256-byte aligned pieces): A = feat as hi / lo rows
+// [M][Kp], then W_ih of both directions as hi / lo rows [8H][Kp].  cnn8 of the whole-path eval forward writes A itself, the GEMM
+// reads it: both sides take their addresses from here.  (A prepared blob keeps its W halves in pieces of nw bytes each.)
+struct VsLstmSplitLayout { int Kp; size_t na, nw, Ah, Al, Wh, Wl; };
+inline VsLstmSplitLayout vs_lstm_split_layout(long long M, int K, int H) {
+  const int Kp = (K + VS_GEMM_KPAD - 1) / VS_GEMM_KPAD * VS_GEMM_KPAD;
+  const size_t na = align_up((size_t)M * Kp * 2), nw = align_up((size_t)8 * H * Kp * 2);
+  return {Kp, na, nw, /*Ah*/ 0, /*Al*/ na, /*Wh*/ 2 * na, /*Wl*/ 2 * na + nw};
+}
+// whether the pre-split form of that GEMM runs out of `scratch` -- A alone when W_ih arrives prepared, else all four arrays.  The
+// one test of both sides: cnn8 asks it before it writes the A operand, the GEMM before it reads one.
+bool vs_lstm_rows_fit(int M, int K, int H, const void* scratch, size_t scratch_bytes, bool prepared);
+// What the caller of the LSTM input GEMM has ready: W_ih prepared (vs_prepare_weights: its scale and split halves, or for
+// VS_MATH_BF16 its bf16 rows in `wh`, are read, not rebuilt) and / or the A operand already in scratch.
+struct VsLstmGemmReady {
+  const float* wscale2 = nullptr;
+  const _Float16 *wh = nullptr, *wl = nullptr;
+  bool feat_bf16 = false;      // VS_MATH_BF16: the bf16 copy of feat is already in scratch
+  bool feat_rows = false;      // VS_MATH_F16X3: cnn8 wrote the split A operand and its scale (gemm_scales[0..1])
+};
 // The LSTM input projection x @ [W_ih; W_ih_reverse]^T (+ per-utterance row bias) in either
 // arithmetic.  gemm_scales: 16 floats of scratch that must survive until the backward pass in
 // training: [0..1] scale of feat, [2..3] scale of the two W_ih, [4..5] uint |max| scratch.
 int vs_lstm_input_gemm_impl(int math, const float* feat, int K, const float* w_ih0, const float* w_ih1, int H, int KE,
                             float* xg, int M, const float* rowbias, int T, float* gemm_scales,
-                            void* scratch, size_t scratch_bytes, hipStream_t, const float* prep_wscale2 = nullptr,
-                            const _Float16* prep_wh = nullptr, const _Float16* prep_wl = nullptr,
-                            bool feat_bf16_ready = false /* VS_MATH_BF16: the bf16 copy of feat is already in scratch */,
-                            bool feat_rows_ready = false /* VS_MATH_F16X3: cnn8 wrote the split A operand + its scale (vs_lstm_rows_fit) */);
-bool vs_lstm_rows_fit(int M, int K, int H, const void* scratch, size_t scratch_bytes, bool prepared);
+                            void* scratch, size_t scratch_bytes, hipStream_t, const VsLstmGemmReady& ready = VsLstmGemmReady());
 int vs_lstm_split_wih_impl(int math, const float* w_ih0, const float* w_ih1, int H, int K, int KE, unsigned* amax1,
                            float* w_scale2, _Float16* Wh, _Float16* Wl, hipStream_t);
 int vs_conv64_pack_f16_impl(const float* w, _Float16* wp, int KT, int KF, int transpose_flip, unsigned* amax_scratch,
@@ -263,6 +280,6 @@ int vs_bilstm_bwd_recurrent_impl(const float* wpt, float* state, float* gates, c
 int vs_sigmoid_bwd_impl(const float* dmask, const float* mask, float* dlogits, long long n, hipStream_t);
 int vs_sigmoid_bwd_rows_impl(const float* dmask, const float* mask, float* dlogits, long long rows, int N, void* rows_bf16, int Kp, hipStream_t);
 int vs_colsum_impl(const float* x, int ld, int groups, int rows, int N, float* out, int ldo, hipStream_t);
-// rows t >= lengths[b] of a [B][T][row_bytes] array := 0 (the ragged eval forward: capi.hip)
+// rows t >= lengths[b] of a [B][T][row_bytes] array := 0 (the ragged eval forward: forward.hip)
 // (share > 1: item b ends at lengths[b / share] -- the K masks of one mixture)
 int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t, int share = 1);

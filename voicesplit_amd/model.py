@@ -211,19 +211,22 @@ class _MaskNet(nn.Module):
             self.__dict__.pop("_prepared", None)     # the eval-mode weight cache is not kept through training
         return super().train(mode)
 
+    def _prepared_for(self, sd, dims):
+        """Eval mode (validation(), test.py, serving): the weight-only work of the forward is done once and kept until a
+        parameter or a running statistic changes (tensor identity + version counters)."""
+        prep = self.__dict__.get("_prepared")
+        if prep is None or not prep.matches(sd, dims):
+            prep = ops.PreparedWeights(sd, dims)
+            self.__dict__["_prepared"] = prep
+        return prep
+
     def _run(self, x, dvec):
         x = x.contiguous()
         dvec = dvec.contiguous()
         dims = self._dims(x.shape[0], x.shape[1])
         sd = self._tensors()                      # only data pointers and version counters are read: no detach needed
         if not self.training:
-            # eval mode (validation(), test.py, serving): the weight-only work of the forward is done once and
-            # kept until a parameter or a running statistic changes (tensor identity + version counters)
-            prep = self.__dict__.get("_prepared")
-            if prep is None or not prep.matches(sd, dims):
-                prep = ops.PreparedWeights(sd, dims)
-                self.__dict__["_prepared"] = prep
-            return ops.forward_prepared(sd, prep, x.detach(), dvec.detach(), dims, self.conv_act)
+            return ops.forward_prepared(sd, self._prepared_for(sd, dims), x.detach(), dvec.detach(), dims, self.conv_act)
         self.__dict__.pop("_prepared", None)
         mask = ops.forward(sd, x.detach(), dvec.detach(), dims, self.conv_act, training=True)
         self._bump_bn_counters()
@@ -298,10 +301,7 @@ class _MaskNet(nn.Module):
         dvec = speaker_embedding.contiguous()
         dims = self._dims(x.shape[0], x.shape[1])
         sd = self._tensors()
-        prep = self.__dict__.get("_prepared")
-        if prep is None or not prep.matches(sd, dims):
-            prep = ops.PreparedWeights(sd, dims)
-            self.__dict__["_prepared"] = prep
+        prep = self._prepared_for(sd, dims)
         return ops.forward_prepared(sd, prep, x, dvec, dims, self.conv_act, lengths=lengths)
 
     def forward_multi(self, x, speaker_embeddings, lengths=None):
@@ -321,10 +321,7 @@ class _MaskNet(nn.Module):
         dvecs = speaker_embeddings.contiguous()
         dims = self._dims(x.shape[0], x.shape[1])
         sd = self._tensors()
-        prep = self.__dict__.get("_prepared")
-        if prep is None or not prep.matches(sd, dims):
-            prep = ops.PreparedWeights(sd, dims)
-            self.__dict__["_prepared"] = prep
+        prep = self._prepared_for(sd, dims)
         return ops.forward_prepared_multi(sd, prep, x, dvecs, dims, self.conv_act, lengths=lengths)
 
     def forward(self, x, speaker_embedding):

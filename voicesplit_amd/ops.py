@@ -290,62 +290,53 @@ def bilstm_multi(sd, feat, dvecs, dims: VsDims, lengths=None, workspace=None) ->
     return out
 
 
-def conv_stack(sd, x, dims: VsDims, conv_act: str, training: bool = False, workspace=None) -> torch.Tensor:
+def conv_stack(sd, x, dims: VsDims, conv_act: str, training: bool = False, workspace=None, lengths=None) -> torch.Tensor:
+    """lengths (eval mode): a padded batch, rows t < lengths[b] as of the item alone (rows behind: finite, unspecified)."""
     lib = _lib.load()
     _dev_check(x, "x")
     params = pack_params(sd)
     ws = workspace if workspace is not None else get_workspace(dims, x.device)
     feat = torch.empty(dims.B, dims.T, 8 * dims.F, dtype=torch.float32, device=x.device)
+    lead = (ctypes.byref(dims), ctypes.byref(params), _p(x))
+    tail = (_p(ws), ws.numel(), _p(feat), _stream())
+    if lengths is not None:
+        if training:
+            raise ValueError("conv_stack: per-item lengths are an eval-mode form")
+        lens = device_lengths(lengths, dims.B, dims.T, x.device)
+        with torch.cuda.device(x.device):
+            check(lib.vs_conv_stack_fwd_ragged(*lead, _p(lens), ACT_CODES[conv_act], *tail), "vs_conv_stack_fwd_ragged")
+        return feat
     with torch.cuda.device(x.device):
-        rc = lib.vs_conv_stack_fwd(ctypes.byref(dims), ctypes.byref(params), _p(x), ACT_CODES[conv_act],
-                                   BN_TRAIN if training else BN_EVAL, _p(ws), ws.numel(), _p(feat), _stream())
-    check(rc, "vs_conv_stack_fwd")
+        check(lib.vs_conv_stack_fwd(*lead, ACT_CODES[conv_act], BN_TRAIN if training else BN_EVAL, *tail), "vs_conv_stack_fwd")
     return feat
 
 
 def conv_stack_ragged(sd, x, lengths, dims: VsDims, conv_act: str, workspace=None) -> torch.Tensor:
-    """Eval-mode features of a padded batch, rows t < lengths[b] as of the item alone (rows behind: finite, unspecified)."""
-    lib = _lib.load()
-    _dev_check(x, "x")
-    params = pack_params(sd)
-    lens = device_lengths(lengths, dims.B, dims.T, x.device)
-    ws = workspace if workspace is not None else get_workspace(dims, x.device)
-    feat = torch.empty(dims.B, dims.T, 8 * dims.F, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.vs_conv_stack_fwd_ragged(ctypes.byref(dims), ctypes.byref(params), _p(x), _p(lens), ACT_CODES[conv_act],
-                                          _p(ws), ws.numel(), _p(feat), _stream())
-    check(rc, "vs_conv_stack_fwd_ragged")
-    return feat
+    return conv_stack(sd, x, dims, conv_act, workspace=workspace, lengths=lengths)
 
 
-def bilstm(sd, feat, dvec, dims: VsDims, workspace=None) -> torch.Tensor:
+def bilstm(sd, feat, dvec, dims: VsDims, workspace=None, lengths=None) -> torch.Tensor:
+    """lengths: a padded batch, a zero state at each item's own first and last frame; rows t >= lengths[b] are 0."""
     lib = _lib.load()
     _dev_check(feat, "feat")
     _dev_check(dvec, "speaker_embedding")
     params = pack_params(sd)
     ws = workspace if workspace is not None else get_workspace(dims, feat.device)
     out = torch.empty(dims.B, dims.T, 2 * dims.H, dtype=torch.float32, device=feat.device)
+    lead = (ctypes.byref(dims), ctypes.byref(params), _p(feat), _p(dvec))
+    tail = (_p(ws), ws.numel(), _p(out), _stream())
+    if lengths is not None:
+        lens = device_lengths(lengths, dims.B, dims.T, feat.device)
+        with torch.cuda.device(feat.device):
+            check(lib.vs_bilstm_fwd_ragged(*lead, _p(lens), *tail), "vs_bilstm_fwd_ragged")
+        return out
     with torch.cuda.device(feat.device):
-        rc = lib.vs_bilstm_fwd(ctypes.byref(dims), ctypes.byref(params), _p(feat), _p(dvec), _p(ws), ws.numel(),
-                               _p(out), _stream())
-    check(rc, "vs_bilstm_fwd")
+        check(lib.vs_bilstm_fwd(*lead, *tail), "vs_bilstm_fwd")
     return out
 
 
 def bilstm_ragged(sd, feat, dvec, lengths, dims: VsDims, workspace=None) -> torch.Tensor:
-    """BiLSTM of a padded batch with a zero state at each item's own first and last frame; rows t >= lengths[b] are 0."""
-    lib = _lib.load()
-    _dev_check(feat, "feat")
-    _dev_check(dvec, "speaker_embedding")
-    params = pack_params(sd)
-    lens = device_lengths(lengths, dims.B, dims.T, feat.device)
-    ws = workspace if workspace is not None else get_workspace(dims, feat.device)
-    out = torch.empty(dims.B, dims.T, 2 * dims.H, dtype=torch.float32, device=feat.device)
-    with torch.cuda.device(feat.device):
-        rc = lib.vs_bilstm_fwd_ragged(ctypes.byref(dims), ctypes.byref(params), _p(feat), _p(dvec), _p(lens), _p(ws), ws.numel(),
-                                      _p(out), _stream())
-    check(rc, "vs_bilstm_fwd_ragged")
-    return out
+    return bilstm(sd, feat, dvec, dims, workspace=workspace, lengths=lengths)
 
 
 def zero_tail_rows(t: torch.Tensor, lengths) -> torch.Tensor:
