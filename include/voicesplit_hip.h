@@ -517,7 +517,8 @@ int vs_conv64_wgrad_f16x3(const float* dz, const float* in, float* partials, flo
 /* which split-f16 weight-gradient kernel vs_conv64_wgrad_f16x3 / vs_backward launch: 0 = by problem
  * size (default: a ring kernel once every workgroup gets >= 2 columns -- the four-wave form for 5x5 --
  * else the kt-split kernel), 1 = eight-wave ring, 2 = kt-split, 3 = four-wave ring (5x5; 7x1 falls back
- * to the eight-wave ring).  Process-wide; returns -1 for an unknown mode. */
+ * to the eight-wave ring).  Process-wide; returns -1 for any other mode and keeps the current one.  (The timing
+ * ablations of the four-wave kernel are instances of `make ABLATION=1` libraries, selected by mode 3 + VS_OPT_ABLATION.) */
 int vs_set_wgrad_kernel(int mode);
 /* which 5x5 split-f16 forward / data-gradient kernel vs_conv64_f16x3_fwd and the whole-path calls
  * launch: 0 = default (the persistent pipelined kernel, csrc/conv_f16x3_pk.hip), 1 = one tile per
@@ -555,9 +556,11 @@ enum vs_option {
                                  contractions' LDS-DMA kernel over bf16 copies of their operands (relu mask in the epilogue); 0 = the generic
                                  kernel (in-flight conversion).  Default 1.  Same operand roundings, fp32 summation order differs.
                                  VOICESPLIT_HEAD_BWD_GEMM */
-  VS_OPT_ABLATION = 4,        /* libraries built with `make ABLATION=1` only (tools/wgrad_ablation.py, tools/split_conv_micro.py, tools/gemm_micro.py):
-                                 selects a TIMING-ABLATION instance of the weight-gradient / split-f16 conv / bf16 GEMM kernels (results are
-                                 meaningless).  Ignored by the product build.  VOICESPLIT_ABLATION */
+  VS_OPT_ABLATION = 4,        /* libraries built with `make ABLATION=1` only (tools/wgrad_ablation.py, tools/split_conv_micro.py, tools/gemm_micro.py,
+                                 tools/conv_bench wgrad): selects a TIMING-ABLATION instance of the weight-gradient / split-f16 conv / bf16 GEMM
+                                 kernels (results are meaningless); the NCHW split-f16 weight gradient looks at it only while
+                                 vs_set_wgrad_kernel(3) pins its four-wave kernel.  Ignored by the product build, except that this pinned kernel
+                                 refuses to launch with a value other than 0 (the instances are not in the library).  VOICESPLIT_ABLATION */
   VS_OPT_DETERMINISTIC = 5,   /* VS_MATH_BF16 training step (vs_forward_train, vs_backward, vs_sisnr_loss): 1 = every partial sum that workgroups
                                  add to shared slots with fp64 atomics (BatchNorm statistics, their backward sums, cnn1's input moments,
                                  the loss head's moments) is added in WORKGROUP ORDER (the workgroups of such a launch that add to the same

@@ -62,6 +62,28 @@ class _wgrad_kernel:
         _lib.load().vs_set_wgrad_kernel(0)
 
 
+def test_set_wgrad_kernel_accepts_modes_0_to_3_only():
+    """0 = auto, 1 = eight-wave ring, 2 = kt-split, 3 = four-wave ring; anything else (the former 100 + ablation modes included) is
+    refused and leaves the mode where it was.  The mode has no getter, so it is read off the bits: the three pinned 5x5 kernels sum
+    in three different orders, and after every refusal under mode 2 the weight gradient must still be the kt-split kernel's."""
+    from voicesplit_amd import _lib, ops
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(3)
+    dz, x = (torch.randn(2, 64, 19, 37, generator=g).to(dev()) for _ in range(2))
+    try:
+        assert lib.vs_set_wgrad_kernel(0) == 0
+        dw = {}
+        for mode in (1, 3, 2):
+            assert lib.vs_set_wgrad_kernel(mode) == 0
+            dw[mode] = ops.conv64_wgrad(dz, x, 5, 5, 1, math="f16x3")
+        assert not torch.equal(dw[1], dw[2]) and not torch.equal(dw[3], dw[2]) and not torch.equal(dw[1], dw[3])
+        for bad in (4, 100, 101):
+            assert lib.vs_set_wgrad_kernel(bad) == -1
+            assert torch.equal(ops.conv64_wgrad(dz, x, 5, 5, 1, math="f16x3"), dw[2]), bad
+    finally:
+        assert lib.vs_set_wgrad_kernel(0) == 0
+
+
 def _conv_ref(x, w, dil):
     KT, KF = w.shape[2], w.shape[3]
     return F.conv2d(F.pad(x, (KF // 2, KF // 2, dil * (KT // 2), dil * (KT // 2))), w, dilation=(dil, 1))

@@ -103,7 +103,8 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (argc > 3 && !strcmp(argv[3], "wgrad")) {
-    // weight-gradient ring kernel (5x5): default vs timing ablations, random and zero operands
+    // weight-gradient ring kernels (5x5) and the timing ablations of the four-wave one, random and zero operands.
+    // Needs a library built with `make ABLATION=1` (the ablation instances are not in the product library).
     const int B = Bbig, T = 301, F = 601;
     const long long n = (long long)B * 64 * T * F;
     float *dz, *in, *part, *dw, *dw2, *scr;
@@ -120,8 +121,9 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     const double gflop = 2.0 * 64 * 64 * 25 * (double)B * T * F / 1e9;
-    auto timeit = [&](int mode, int dil, const char* what) {
+    auto timeit = [&](int mode, int abl, int dil, const char* what) {
       VS(vs_set_wgrad_kernel(mode));
+      VS(vs_set_option(VS_OPT_ABLATION, abl));
       CK(hipMemset(scr, 0, 64));
       VS(vs_conv64_wgrad_f16x3(dz, in, part, dw, scr, B, T, F, 5, 5, dil, nullptr));
       CK(hipEventRecord(e0));
@@ -131,32 +133,41 @@ int main(int argc, char** argv) {
       float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= reps;
       printf("  dil=%-2d %-52s %.3f ms  (%.0f TF algorithmic; includes 2 operand |max| passes ~0.25 ms)\n", dil, what, ms, gflop / ms);
     };
-    if (argc > 4) {          // one variant only (for counter passes): tools/conv_bench 64 3 wgrad <mode>
-      timeit(atoi(argv[4]), 1, "selected variant");
+    // every run of this mode times ablation instances: a product library refuses the first one, so ask before anything is timed
+    VS(vs_set_wgrad_kernel(3));
+    VS(vs_set_option(VS_OPT_ABLATION, 1));
+    CK(hipMemset(scr, 0, 64));
+    if (vs_conv64_wgrad_f16x3(dz, in, part, dw, scr, B, T, F, 5, 5, 1, nullptr)) {
+      printf("conv_bench wgrad needs a library built with `make ABLATION=1`: %s\n", vs_last_error());
+      return 3;
+    }
+    if (argc > 4) {          // one ablation only (for counter passes): tools/conv_bench 64 3 wgrad <ablation>
+      timeit(3, atoi(argv[4]), 1, "selected ablation of the four-wave kernel");
       return 0;
     }
     printf("wgrad ring kernel 5x5, B=%d (random operands):\n", B);
-    for (int dil : {1, 4, 16}) timeit(1, dil, "eight-wave ring kernel (round 1)");
-    for (int dil : {1, 4, 16}) timeit(3, dil, "four-wave ring kernel");
-    timeit(164, 1, "  - every load out of range (no memory access)");
-    timeit(168, 1, "  - loads only + out of range");
-    timeit(228, 1, "  - every load from the slab's first 64 KB (L2-hot)");
-    timeit(232, 1, "  - loads only + L2-hot");
-    timeit(356, 1, "  - all staging pieces behind K block 3");
-    timeit(612, 1, "  - same bytes per step as ONE contiguous 28 KB piece (HBM-cold, one page)");
-    timeit(616, 1, "  - loads only + contiguous piece");
-    timeit(101, 1, "  - fragments read once per step");
-    timeit(102, 1, "  - no staging (loads, conversion, LDS writes)");
-    timeit(108, 1, "  - no barriers");
-    timeit(104, 1, "  - loads issued + waited for, no conversion / LDS writes");
-    timeit(116, 1, "  - conversion + LDS writes, no loads");
-    timeit(103, 1, "  - no staging, fragments once");
-    timeit(111, 1, "  - MFMA stream only");
+    for (int dil : {1, 4, 16}) timeit(1, 0, dil, "eight-wave ring kernel (round 1)");
+    for (int dil : {1, 4, 16}) timeit(3, 0, dil, "four-wave ring kernel");
+    timeit(3, 64, 1, "  - every load out of range (no memory access)");
+    timeit(3, 68, 1, "  - loads only + out of range");
+    timeit(3, 128, 1, "  - every load from the slab's first 64 KB (L2-hot)");
+    timeit(3, 132, 1, "  - loads only + L2-hot");
+    timeit(3, 256, 1, "  - all staging pieces behind K block 3");
+    timeit(3, 512, 1, "  - same bytes per step as ONE contiguous 28 KB piece (HBM-cold, one page)");
+    timeit(3, 516, 1, "  - loads only + contiguous piece");
+    timeit(3, 1, 1, "  - fragments read once per step");
+    timeit(3, 2, 1, "  - no staging (loads, conversion, LDS writes)");
+    timeit(3, 8, 1, "  - no barriers");
+    timeit(3, 4, 1, "  - loads issued + waited for, no conversion / LDS writes");
+    timeit(3, 16, 1, "  - conversion + LDS writes, no loads");
+    timeit(3, 3, 1, "  - no staging, fragments once");
+    timeit(3, 11, 1, "  - MFMA stream only");
     CK(hipMemset(in, 0, n * 4));
     printf("same, all-zero input operand:\n");
-    timeit(1, 1, "eight-wave ring kernel, zero input");
-    timeit(3, 1, "four-wave ring kernel, zero input");
-    timeit(111, 1, "  - MFMA stream only, zero input");
+    timeit(1, 0, 1, "eight-wave ring kernel, zero input");
+    timeit(3, 0, 1, "four-wave ring kernel, zero input");
+    timeit(3, 11, 1, "  - MFMA stream only, zero input");
+    VS(vs_set_option(VS_OPT_ABLATION, 0));
     VS(vs_set_wgrad_kernel(0));
     return 0;
   }

@@ -404,11 +404,6 @@ void nhwc_bn_bwd_first_kernel(const u4v* __restrict__ da, const u4v* __restrict_
   }
 }
 
-__global__ void nhwc_cvt_f64_f32_kernel(const double* __restrict__ src, float* __restrict__ dst, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = (float)src[i];
-}
-
 // cnn8 backward in one pass over a7: din[b][t][f][ci] = sum_co w[co][ci] dz8[b][t][co][f]  (data gradient, bf16) and
 // dw[co][ci] = sum_pixels dz8[..][co][..] a7[..][ci]  (weight gradient: per-workgroup partial sums part[block][co][ci])
 // DYACT >= 0: the data gradient is turned into dy = din * act'(z7 * scale + shift) before it is stored, and the
@@ -1022,9 +1017,7 @@ int vs_nhwc_bn_bwd_first_from_dy_impl(const void* dy, const void* z, const float
   const dim3 grid(stream_blocks(32, npix)), block(256);
   hipLaunchKernelGGL(nhwc_bn_bwd_first_kernel<VS_ACT_NONE>, grid, block, 0, stream, reinterpret_cast<const u4v*>(dy), reinterpret_cast<const u4v*>(z),
                      x, npix, F, scale, scale, coef, acc);
-  hipLaunchKernelGGL(nhwc_cvt_f64_f32_kernel, dim3(2), dim3(256), 0, stream, acc, dw, 448);
-  VS_LAUNCH_CHECK();
-  return 0;
+  return vs_cvt_f64_f32_impl(acc, dw, 448, stream);
 }
 
 // cnn1: the same backward with pass 2 contracted against the input on the spot: dw [64][7] (dz1 is not written)
@@ -1050,9 +1043,7 @@ int vs_nhwc_bn_act_bwd_first_impl(const void* da, const void* z, const float* x,
   if (act == VS_ACT_MISH) hipLaunchKernelGGL(nhwc_bn_bwd_first_kernel<VS_ACT_MISH>, grid, block, 0, stream, g, zz, x, npix, F, scale, shift, coef, acc);
   else if (act == VS_ACT_RELU) hipLaunchKernelGGL(nhwc_bn_bwd_first_kernel<VS_ACT_RELU>, grid, block, 0, stream, g, zz, x, npix, F, scale, shift, coef, acc);
   else hipLaunchKernelGGL(nhwc_bn_bwd_first_kernel<VS_ACT_NONE>, grid, block, 0, stream, g, zz, x, npix, F, scale, shift, coef, acc);
-  hipLaunchKernelGGL(nhwc_cvt_f64_f32_kernel, dim3(2), dim3(256), 0, stream, acc, dw, 448);
-  VS_LAUNCH_CHECK();
-  return 0;
+  return vs_cvt_f64_f32_impl(acc, dw, 448, stream);
 }
 
 // cnn8 backward: dz8 [B][T][8][F] fp32, a7 [B][T][F][64] bf16 -> din (bf16, same layout as a7) and dw [8][64];

@@ -89,7 +89,19 @@ void zero_tail_rows_kernel(unsigned* __restrict__ p, int T, long long row_words,
   }
 }
 
+__global__ void cvt_f64_f32_kernel(const double* __restrict__ src, float* __restrict__ dst, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = (float)src[i];
+}
+
 }  // namespace
+
+// dst[i] = (float)src[i]: the fp64 accumulators of cnn1's weight gradient (conv_bwd.hip, nhwc_edge.hip)
+int vs_cvt_f64_f32_impl(const double* src, float* dst, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(cvt_f64_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, src, dst, n);
+  VS_LAUNCH_CHECK();
+  return 0;
+}
 
 int vs_zero_tail_rows_impl(void* ptr, int B, int T, size_t row_bytes, const int* lengths, hipStream_t stream, int share) {
   VS_REQUIRE(ptr && lengths, "zero_tail_rows: NULL argument");

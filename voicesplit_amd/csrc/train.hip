@@ -803,7 +803,7 @@ int convs_bwd_nchw(const Step& st, SideJoin& sj, const float* x, const vs_grads*
       VsProfScope ps(VS_PROF_BWD_WGRAD + i, sj.to());
       if (f16x3) {
         if (int rc = vs_conv64_wgrad_f16x3_impl(gbuf[cur], st.at<float>(L.a[l - 1]), sc_bwd, st.cs + VS_SCALE_SLOT_FLOATS * l,
-                                                st.part, g->conv[l].weight, B, T, F, kMid[i].kt, kMid[i].kf, kMid[i].dil, sj.to(), st.d->math)) return rc;
+                                                st.part, g->conv[l].weight, B, T, F, kMid[i].kt, kMid[i].kf, kMid[i].dil, sj.to())) return rc;
       } else {
         if (int rc = vs_conv64_wgrad_impl(gbuf[cur], st.at<float>(L.a[l - 1]), st.part, g->conv[l].weight, B, T, F,
                                           kMid[i].kt, kMid[i].kf, kMid[i].dil, sj.to())) return rc;

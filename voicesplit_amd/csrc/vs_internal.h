@@ -212,11 +212,12 @@ int vs_bn_apply_feat_bf16_impl(const float* x, float* y, void* yb, int Kp, int B
                                hipStream_t);
 int vs_bn_eval_consts_impl(const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps, int C,
                            float* scale, float* shift, float* mean_out, float* invstd_out, hipStream_t);
+// wgrad_f16x3.hip
+int vs_conv64_wgrad_f16x3_impl(const float* dz, const float* in, const float* dz_scale2, const float* in_scale2,
+                               float* part, float* dw, int B, int T, int F, int KT, int KF, int dil, hipStream_t);
 // conv_bwd.hip
 int vs_conv64_wgrad_impl(const float* dz, const float* in, float* part, float* dw, int B, int T, int F, int KT, int KF, int dil, hipStream_t);
-int vs_conv64_wgrad_f16x3_impl(const float* dz, const float* in, const float* dz_scale2, const float* in_scale2,
-                               float* part, float* dw, int B, int T, int F, int KT, int KF, int dil, hipStream_t,
-                               int math = VS_MATH_CODE_F16X3);
+int vs_conv64_wgrad_reduce_impl(const float* part, int G, int NT, float* dw, const float* dz_scale2 /* NULL: unscaled */, const float* in_scale2, hipStream_t);
 int vs_bn_act_bwd_impl(const float* da, const float* z, float* dz, int C, long long R, int L, int act, int train,
                        const float* scale, const float* shift, const float* mean, const float* invstd,
                        float* dgamma, float* dbeta, float* dbias, double* stats, float* coef, unsigned* amax_out, hipStream_t);
@@ -279,6 +280,7 @@ int vs_bilstm_bwd_recurrent_impl(const float* wpt, float* state, float* gates, c
 // reduce.hip
 int vs_sigmoid_bwd_impl(const float* dmask, const float* mask, float* dlogits, long long n, hipStream_t);
 int vs_sigmoid_bwd_rows_impl(const float* dmask, const float* mask, float* dlogits, long long rows, int N, void* rows_bf16, int Kp, hipStream_t);
+int vs_cvt_f64_f32_impl(const double* src, float* dst, int n, hipStream_t);
 int vs_colsum_impl(const float* x, int ld, int groups, int rows, int N, float* out, int ldo, hipStream_t);
 // rows t >= lengths[b] of a [B][T][row_bytes] array := 0 (the ragged eval forward: forward.hip)
 // (share > 1: item b ends at lengths[b / share] -- the K masks of one mixture)
