@@ -244,6 +244,24 @@ int vs_forward_prepared_multi(const vs_dims* dims, const vs_params* params, cons
 int vs_bilstm_fwd_multi(const vs_dims* dims, const vs_params* params, const float* feat, const float* dvecs, int K,
                         const int* lengths_or_null, void* workspace, size_t workspace_bytes, float* lstm_out, void* stream);
 
+/* ---- the sequence stage with a carried forward state: a stream separated chunk by chunk ---------------------------
+ * The latency-controlled BiLSTM: one call runs model.py:77-82 over the T = dims.T frames [chunk | look-ahead] of a stream.
+ *   forward direction: starts from state_in [B][2][H] (fp32; h, then c; NULL = zero state: the stream's first chunk) and
+ *     hands h and c behind frame keep - 1 (the chunk's last frame, 1 <= keep <= T) to state_out [B][2][H]; rows t >= keep
+ *     of its half of lstm_out are valid forward outputs over the look-ahead frames.  Given the previous call's state_out,
+ *     rows t < keep continue the whole-stream recurrence: in the recurrence's own operand form the hand-over is exact (two
+ *     calls over [0, a) and [a, T) give the forward half of one call over [0, T) bit for bit);
+ *   reverse direction: from a zero state at frame T - 1, as in vs_bilstm_fwd.
+ * state_in and state_out may be the same buffer (h is read by a launch in front of the recurrence, every value of c by the
+ * lane that later writes it).  Input GEMM with row bias, then the tagged persistent
+ * recurrence in its carry mode; with state_in = NULL and keep = T, lstm_out is bit-identical to vs_bilstm_fwd's.
+ * Eval mode only.  Refused with an error code and a message, never computed some other way: VS_MATH_FP32, H > 448 (the flag
+ * kernel), vs_set_lstm_kernel not 0 or 2, a grid that is not resident, keep outside [1, T], NULL state_out.
+ * workspace: vs_workspace_bytes(dims). */
+int vs_bilstm_fwd_carry(const vs_dims* dims, const vs_params* params, const float* feat, const float* dvec,
+                        const float* state_in, float* state_out, int keep,
+                        void* workspace, size_t workspace_bytes, float* lstm_out, void* stream);
+
 /* ---- kernels (unit-test surface) --------------------------------------------------------- */
 /* BN(conv+bias) = conv*scale + shift */
 int vs_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,
@@ -412,6 +430,11 @@ int vs_bilstm_recurrent(const float* xg, const float* packed_whh, float* state, 
 int vs_lstm_pack_math(const float* w_hh_fwd, const float* w_hh_bwd, float* packed, int H, int math, void* stream);
 int vs_bilstm_recurrent_math(const float* xg, const float* packed_whh, float* state, float* out, float* gates_save, float* c_save,
                              int B, int T, int H, int math, void* stream);
+/* The inference recurrence with a carried forward state (the raw form of vs_bilstm_fwd_carry above): state_in [B][2][H]
+ * fp32 (h, then c) or NULL = zero, state_out [B][2][H], 1 <= keep <= T.  math = VS_MATH_F16X3 or VS_MATH_BF16 and H <= 448;
+ * everything else is refused as vs_bilstm_fwd_carry refuses it. */
+int vs_bilstm_recurrent_carry(const float* xg, const float* packed_whh, float* state, float* out, const float* state_in,
+                              float* state_out, int keep, int B, int T, int H, int math, void* stream);
 
 /* =============================================================================================
  * Training: forward that keeps what backward needs + the backward pass itself.

@@ -128,6 +128,97 @@ def separate_speakers_with_reference(model, encoder, wav: torch.Tensor, ref_wavs
     return separate_speakers(model, wav, dvec.view(wav.shape[0], K, -1).contiguous(), audio_cfg)
 
 
+class StreamingSeparator:
+    """``separate`` on a live stream: ``push(samples [B, n * hop_length])`` returns the separated samples that became final
+    ([B, k * hop_length], k >= 0), ``finish()`` the rest; the concatenation covers every pushed sample.  Host glue over
+    ``wav_to_spec`` / ``spec_to_wav`` and ``streaming.StreamingMasker`` (chunks of ``C`` frames, ``R`` frames of look-ahead):
+
+    * STFT: the pending samples are transformed as one segment; its reflect padding reaches ``margin = ceil(n_fft / 2 / hop)``
+      frames in from each end, so frames that close to a segment edge that is not a stream edge are dropped, and the samples
+      they need are kept and transformed again with the next segment;
+    * iSTFT: the masked frames are inverted as one segment; the overlap-add of a sample within ``margin`` frames of a segment
+      edge that is not a stream edge misses frames, so those samples are dropped and their frames are inverted again later.
+
+    A sample is returned once ``latency_samples`` more have been pushed (or at ``finish()``)."""
+
+    def __init__(self, model, dvec: torch.Tensor, audio_cfg, C: int, R: int, trace: bool = False):
+        from .streaming import StreamingMasker
+        self.mask_trace = [] if trace else None  # trace: every block of mask rows, in order
+        self.cfg = audio_cfg
+        self.hop = int(audio_cfg["hop_length"])
+        self.margin = -(-(int(audio_cfg["n_fft"]) // 2) // self.hop)
+        self.masker = StreamingMasker(*model.stream_stages(), dvec, C, R)
+        self.finished = False
+        self._wav, self._w0 = None, 0            # samples from frame _w0 (sample _w0 * hop) on
+        self._hops = 0                           # pushed samples / hop
+        self._frames = 0                         # STFT frames handed to the masker
+        self._spec = self._phase = None          # frames [_s0, _frames)
+        self._mask = None                        # rows [_s0, _rows)
+        self._s0 = self._rows = 0
+        self._out = 0                            # returned samples / hop
+
+    @property
+    def latency_samples(self) -> int:
+        """A returned block starts ``latency_samples`` behind the newest pushed sample: frames the STFT holds back (margin), the
+        masker's chunk, look-ahead and conv halo, and the frames the iSTFT holds back (margin + the frame that closes a hop)."""
+        return (self.masker.latency_frames + 2 * self.margin) * self.hop
+
+    def push(self, samples: torch.Tensor) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("StreamingSeparator: the stream has been finished")
+        if samples.dim() != 2 or samples.shape[1] % self.hop:
+            raise ValueError(f"samples must be [B, n * hop_length = n * {self.hop}], got {tuple(samples.shape)}")
+        self._wav = samples if self._wav is None else torch.cat((self._wav, samples), dim=1)
+        self._hops += samples.shape[1] // self.hop
+        return self._advance()
+
+    def finish(self) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("StreamingSeparator: the stream has been finished")
+        if self._wav is None:
+            raise RuntimeError("StreamingSeparator: finish() on a stream that never received a sample")
+        self.finished = True
+        return self._advance()
+
+    def _advance(self) -> torch.Tensor:
+        m, hop = self.margin, self.hop
+        # analysis: frames [_frames, n_valid) are exact now
+        n_valid = self._hops + 1 if self.finished else max(0, self._hops - m + 1)
+        masks = []
+        if n_valid > self._frames and self._hops > self._w0:
+            spec, phase = wav_to_spec(self._wav.contiguous(), self.cfg)                  # frames [_w0, _hops]
+            spec = spec[:, self._frames - self._w0:n_valid - self._w0]
+            phase = phase[:, self._frames - self._w0:n_valid - self._w0]
+            self._spec = spec if self._spec is None else torch.cat((self._spec, spec), dim=1)
+            self._phase = phase if self._phase is None else torch.cat((self._phase, phase), dim=1)
+            self._frames = n_valid
+            w0 = max(0, self._frames - m)
+            self._wav, self._w0 = self._wav[:, (w0 - self._w0) * hop:], w0
+            masks.append(self.masker.push(spec.contiguous()))
+        if self.finished and self._frames:
+            masks.append(self.masker.finish())
+        for mk in masks:
+            if mk.shape[1]:
+                if self.mask_trace is not None:
+                    self.mask_trace.append(mk)
+                self._mask = mk if self._mask is None else torch.cat((self._mask, mk), dim=1)
+                self._rows += mk.shape[1]
+        # synthesis: samples [_out * hop, done * hop) are exact now
+        done = self._hops if self.finished else self._rows - 1 - m
+        if done <= self._out or self._mask is None:
+            return self._wav.new_empty(self._wav.shape[0], 0)
+        fa = max(0, self._out - m)
+        lo, hi = fa - self._s0, self._rows - self._s0
+        wav = spec_to_wav(self._spec[:, lo:hi].contiguous(), self._phase[:, lo:hi].contiguous(), self.cfg,
+                          mask=self._mask[:, lo:hi].contiguous())                        # samples [fa * hop, (_rows - 1) * hop)
+        out = wav[:, (self._out - fa) * hop:(done - fa) * hop]
+        self._out = done
+        s0 = max(0, self._out - m)
+        self._spec, self._phase, self._mask = self._spec[:, s0 - self._s0:], self._phase[:, s0 - self._s0:], self._mask[:, s0 - self._s0:]
+        self._s0 = s0
+        return out
+
+
 # frames a ragged batch may occupy (items * longest item): 64 clips of 3 s, the batch the workspace of the 3 s path is sized for anyway
 RAGGED_MAX_ITEMS = 64
 RAGGED_MAX_FRAMES = 64 * 301

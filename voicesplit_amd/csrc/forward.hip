@@ -272,6 +272,7 @@ struct Fwd {
   const Prep* prep;            // prepared weights (eval), or NULL
   const int* lengths;          // device [B]: a ragged batch (eval, channels-last arithmetics), or NULL
   const MultiBufs* multi;      // several speakers per mixture, or NULL
+  const VsLstmCarry* carry;    // the recurrence's forward direction from / to a caller-held state (a stream chunk), or NULL
   int B, T, F, H;
   size_t act_bytes;            // one buffer of the conv activation ping-pong
   template <typename U>
@@ -292,10 +293,10 @@ struct Fwd {
 };
 
 Fwd make_fwd(const vs_dims* d, const vs_params* p, void* ws, const vs_ws_layout& L, int conv_act, int bn_mode, hipStream_t stream,
-             const Prep* prep = nullptr, const int* lengths = nullptr, const MultiBufs* multi = nullptr) {
+             const Prep* prep = nullptr, const int* lengths = nullptr, const MultiBufs* multi = nullptr, const VsLstmCarry* carry = nullptr) {
   Fwd f;
   f.d = d; f.p = p; f.ws = ws; f.L = L; f.stream = stream; f.conv_act = conv_act; f.bn_mode = bn_mode; f.train = bn_mode == VS_BN_TRAIN;
-  f.prep = prep; f.lengths = lengths; f.multi = multi;
+  f.prep = prep; f.lengths = lengths; f.multi = multi; f.carry = carry;
   f.B = d->B; f.T = d->T; f.F = d->F; f.H = d->H; f.act_bytes = (size_t)d->B * 64 * d->T * d->F * sizeof(float);
   return f;
 }
@@ -558,7 +559,8 @@ int bilstm(const Fwd& f, const float* feat, const float* dvec, float* lstm_out, 
   // (lengths: the input GEMM above ran over all B*T rows; the recurrence keeps the rows behind an item's end out of its state)
   if (multi)
     return vs_bilstm_recurrent_impl(xg, packed, multi->lstm_state, lstm_out, nullptr, nullptr, NS, T, H, f.stream, d->math, f.lengths, dvbias, multi->K);
-  return vs_bilstm_recurrent_impl(xg, packed, f.at<float>(L.lstm_state), lstm_out, nullptr, nullptr, B, T, H, f.stream, d->math, f.lengths);
+  return vs_bilstm_recurrent_impl(xg, packed, f.at<float>(L.lstm_state), lstm_out, nullptr, nullptr, B, T, H, f.stream, d->math, f.lengths,
+                                  nullptr, 1, f.carry);
 }
 
 // ---- stage 3: head, models/voicesplit/model.py:83-87 ----
@@ -783,6 +785,18 @@ int vs_bilstm_fwd_multi(const vs_dims* d, const vs_params* p, const float* feat,
   if (int rc = check_multi_ws(d, K, ws, ws_bytes, &M)) return rc;
   const MultiBufs mb = multi_bufs(ws, M, K);
   return bilstm(make_fwd(d, p, ws, M.base, VS_ACT_NONE, VS_BN_EVAL, (hipStream_t)stream, nullptr, lengths, &mb), feat, dvecs, lstm_out, false);
+}
+
+int vs_bilstm_fwd_carry(const vs_dims* d, const vs_params* p, const float* feat, const float* dvec,
+                        const float* state_in, float* state_out, int keep,
+                        void* ws, size_t ws_bytes, float* lstm_out, void* stream) {
+  if (int rc = check_dims(d)) return rc;
+  if (int rc = vs_lstm_carry_check(d->math, d->H, d->T, keep, state_out, "bilstm_fwd_carry")) return rc;
+  VS_REQUIRE(feat && lstm_out, "bilstm_fwd_carry: NULL argument");
+  vs_ws_layout L;
+  if (int rc = check_ws(d, ws, ws_bytes, &L)) return rc;
+  const VsLstmCarry carry{state_in, state_out, keep};
+  return bilstm(make_fwd(d, p, ws, L, VS_ACT_NONE, VS_BN_EVAL, (hipStream_t)stream, nullptr, nullptr, nullptr, &carry), feat, dvec, lstm_out, false);
 }
 
 int vs_head_fwd(const vs_dims* d, const vs_params* p, const float* lstm_out, void* ws, size_t ws_bytes,

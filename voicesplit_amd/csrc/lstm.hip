@@ -1017,9 +1017,25 @@ struct LstmSharedIn {
   int K;                  // sequences per shared row of xg
 };
 
-template <int NP, bool RAGGED, bool SHARED = false>
+//
+// CARRY (stream separation chunk by chunk, vs_bilstm_recurrent_carry): the FORWARD direction starts from a caller-given state instead
+// of zero and hands its state out at one chosen frame, so the next call continues the same recurrence.  h_0 reaches the workgroups the
+// way every later h does: lstm16_seed_kernel, a launch in front of this one on the same stream, writes it into exchange buffer 0 in the
+// operand form below (the reverse direction's slots keep the launcher's zeros), and step 0 polls and multiplies like every other step.
+// c_0 goes straight into wave 0's registers.  When the forward direction finishes frame t = keep - 1, wave 0 stores h and c of that
+// frame in fp32 to state_out [B][2][H] (h, then c), behind the exchange store; the direction runs on to T (its rows t >= keep are the
+// forward outputs over the caller's look-ahead frames).  The h handed out is the fp32 value the exchange store rounds, and the seeding
+// pass rounds it the same way: two calls over [0, a) and [a, T) give the forward half of one call over [0, T) bit for bit.  Hand-off,
+// re-arming, spins and error word are the kernel's own; !CARRY is the kernel as it was (cy unused).
+struct LstmCarry {
+  const float* state_in;  // [B][2][H] fp32: h and c of the forward direction in front of frame 0, or NULL: zero (only c is read here)
+  float* state_out;       // [B][2][H] fp32: h and c of the forward direction behind frame keep - 1
+  int keep;               // 1 <= keep <= T
+};
+
+template <int NP, bool RAGGED, bool SHARED = false, bool CARRY = false>
 __global__ __launch_bounds__(256)
-void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __restrict__ lengths, LstmSharedIn sh) {
+void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __restrict__ lengths, LstmSharedIn sh, LstmCarry cy) {
   __shared__ float sRed[2][3 * 16 * 64];      // by step parity: no barrier separates wave 0's reads of step s from the other waves' writes of step s + 1
   __shared__ int sDead;
   const int tid = threadIdx.x;
@@ -1068,6 +1084,10 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __r
 #pragma unroll
     for (int r = 0; r < 16; ++r) rbv[r] = ok ? rrow[(r >> 2) * a.H + (r & 3)] : 0.f;
   }
+  if (CARRY && wave == 0 && dir == 0 && cy.state_in && b < a.B) {
+    const float4 c0 = *reinterpret_cast<const float4*>(cy.state_in + ((size_t)b * 2 + 1) * a.H + jg * 8 + 4 * half);
+    cprev[0] = c0.x; cprev[1] = c0.y; cprev[2] = c0.z; cprev[3] = c0.w;
+  }
   __syncthreads();
 
 #pragma unroll 1
@@ -1084,7 +1104,7 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __r
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    if (s > 0) {
+    if (CARRY || s > 0) {          // CARRY: buffer 0 holds the seeded h_0 (zeros for the reverse direction)
       const unsigned hoff = (unsigned)((group * NC * NP * 64 + lane) * 16);
       f16x8 h[kMaxC][NP];
       unsigned spins = 0;
@@ -1187,6 +1207,11 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __r
       if (b < a.B) {
         float4* o = reinterpret_cast<float4*>(a.out + ((size_t)b * a.T + t) * (2 * a.H) + (size_t)dir * a.H + jg * 8 + 4 * half);
         *o = make_float4(hv[0], hv[1], hv[2], hv[3]);
+        if (CARRY && dir == 0 && t == cy.keep - 1) {      // the state the next call starts from
+          float4* so = reinterpret_cast<float4*>(cy.state_out + (size_t)b * 2 * a.H + jg * 8 + 4 * half);
+          so[0] = make_float4(hv[0], hv[1], hv[2], hv[3]);
+          so[a.H / 4] = make_float4(cnew[0], cnew[1], cnew[2], cnew[3]);
+        }
         if (a.c_save) {
           float4* cs = reinterpret_cast<float4*>(a.c_save + ((size_t)b * a.T + t) * (2 * a.H) + (size_t)dir * a.H + jg * 8 + 4 * half);
           *cs = make_float4(cnew[0], cnew[1], cnew[2], cnew[3]);
@@ -1200,6 +1225,42 @@ void lstm16_tagged_kernel(Lstm16Args a, void* hbuf2, void* hbuf3, const int* __r
       }
     }
   }
+}
+
+// CARRY's seeding pass: h_0 of the forward direction, state_in [B][2][H] fp32, into exchange buffer 0 in the tagged kernel's operand
+// form -- thread (b, jg) converts the 8 values a producer workgroup jg would have stored for batch column b: the same roundings, the
+// same slot, the same sentinel guard.  Plain stores: the kernel boundary publishes them.  Everything else in buffer 0 (reverse
+// direction, padding columns) keeps the launcher's zeros.
+template <int NP>
+__global__ void lstm16_seed_kernel(const float* __restrict__ state_in, u32x4_t* __restrict__ hbuf0, int B, int H) {
+  const int HQ = H / 8, NC = (H + 15) / 16;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long long)B * HQ) return;
+  const int jg = idx % HQ, b = idx / HQ;
+  const int bt = b >> 5, l31 = b & 31;
+  const float* hrow = state_in + (size_t)b * 2 * H + jg * 8;
+  const float4 lo4 = *reinterpret_cast<const float4*>(hrow), hi4 = *reinterpret_cast<const float4*>(hrow + 4);
+  const float full[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
+  u32x4_t vh, vl;
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (NP == 2) {
+      const float x0 = full[2 * j] * kHScale, x1 = full[2 * j + 1] * kHScale;
+      const h2 hh = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
+      vh[j] = __builtin_bit_cast(unsigned, hh);
+      vl[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x0 - (float)hh[0], x1 - (float)hh[1]));
+      vl[j] = vl[j] == kSentinel ? 0x7FFF7E00u : vl[j];
+    } else {
+      const h2 hh = {(_Float16)full[2 * j], (_Float16)full[2 * j + 1]};
+      vh[j] = __builtin_bit_cast(unsigned, hh);
+    }
+    vh[j] = vh[j] == kSentinel ? 0x7FFF7E00u : vh[j];
+  }
+  // group = (dir 0) * NBT + bt; [group][NC][NP][64 lane]
+  const size_t slot = (((size_t)bt * NC + (jg >> 1)) * NP) * 64 + (jg & 1) * 32 + l31;
+  hbuf0[slot] = vh;
+  if (NP == 2) hbuf0[slot + 64] = vl;
 }
 
 struct Lstm16BwdArgs {
@@ -1421,6 +1482,30 @@ extern "C" int vs_set_lstm_kernel(int mode) {
   return 0;
 }
 
+// What the carry form can be refused for without looking at the device: checked by both C entries before anything else
+int vs_lstm_carry_check(int math, int H, int T, int keep, const float* state_out, const char* what) {
+  VS_REQUIRE(state_out != nullptr, "%s: state_out is NULL", what);
+  VS_REQUIRE(keep >= 1 && keep <= T, "%s: keep=%d outside 1 <= keep <= T = %d", what, keep, T);
+  VS_REQUIRE(math == VS_MATH_CODE_F16X3 || math == VS_MATH_CODE_BF16,
+             "%s: the carried state is served by VS_MATH_F16X3 and VS_MATH_BF16; VS_MATH_FP32 has no carry recurrence", what);
+  VS_REQUIRE(H <= 64 * kMaxC, "%s: H=%d: the carried state is served by the tagged recurrence (H <= %d); the flag kernel starts from a zero state",
+             what, H, 64 * kMaxC);
+  VS_REQUIRE(g_lstm_kernel == 0 || g_lstm_kernel == 2,
+             "%s: vs_set_lstm_kernel(%d) selects a recurrence that starts from a zero state; the carried state needs mode 0 or 2", what, g_lstm_kernel);
+  return 0;
+}
+
+// the raw carry recurrence beside vs_bilstm_recurrent_math (see the header)
+extern "C" int vs_bilstm_recurrent_carry(const float* xg, const float* packed_whh, float* state, float* out, const float* state_in,
+                                         float* state_out, int keep, int B, int T, int H, int math, void* stream) {
+  VS_REQUIRE(math == VS_MATH_CODE_FP32 || math == VS_MATH_CODE_F16X3 || math == VS_MATH_CODE_BF16, "bilstm_recurrent_carry: unknown math %d", math);
+  VS_REQUIRE(B > 0 && T > 0 && H > 0 && H % 8 == 0, "bilstm_recurrent_carry: bad shape B=%d T=%d H=%d (H must be a multiple of 8)", B, T, H);
+  if (int rc = vs_lstm_carry_check(math, H, T, keep, state_out, "bilstm_recurrent_carry")) return rc;
+  VS_REQUIRE(xg && packed_whh && state && out, "bilstm_recurrent_carry: NULL argument");
+  const VsLstmCarry carry{state_in, state_out, keep};
+  return vs_bilstm_recurrent_impl(xg, packed_whh, state, out, nullptr, nullptr, B, T, H, (hipStream_t)stream, math, nullptr, nullptr, 1, &carry);
+}
+
 namespace {
 // A persistent launch whose spin gave up (a workgroup was not resident: the error word is 1) has produced garbage.
 // The word is only read by callers that ask (vs_lstm_status), so the result itself is made unusable: NaN in the first
@@ -1445,9 +1530,13 @@ hipError_t launch_resident(const void* kernel, dim3 grid, dim3 block, Args& a, h
 // Persistent kernel: h ping, h pong (fragment order), then the flag words + the error word.
 // rowbias != NULL: the shared-input form (lstm16_tagged_kernel<.., SHARED>): B sequences n = m*K + k read xg [B / K][T][8H] at mixture
 // n / K and add rowbias [B][8H]; lengths, when given, are per mixture [B / K]; out [B][T][2H]
+// carry != NULL: the carry form (lstm16_tagged_kernel<.., CARRY>): the forward direction starts from carry->state_in and hands its
+// state behind frame carry->keep - 1 to carry->state_out
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
-                             int B, int T, int H, hipStream_t stream, int math, const int* lengths, const float* rowbias, int K) {
+                             int B, int T, int H, hipStream_t stream, int math, const int* lengths, const float* rowbias, int K,
+                             const VsLstmCarry* carry) {
   VS_REQUIRE(B > 0 && T > 0 && H > 0 && H % 8 == 0, "lstm: bad shape B=%d T=%d H=%d (H must be a multiple of 8)", B, T, H);
+  if (carry) { if (int rc = vs_lstm_carry_check(math, H, T, carry->keep, carry->state_out, "lstm")) return rc; }
   VS_REQUIRE(rowbias ? (K >= 1 && B % K == 0) : K == 1, "lstm: %d sequences do not share rows of xg in groups of K=%d", B, K);
   const int Bpad = (B + 31) / 32 * 32;
   const size_t per = lstm_state_region(B, H);
@@ -1473,7 +1562,19 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
              "lstm: the shared-input recurrence (several speakers per mixture) is the tagged persistent recurrence in eval mode (dims.math F16X3 or "
              "BF16, H <= %d, 2*H/8 = %d workgroups <= %d CUs, vs_set_lstm_kernel 0 or 2); VS_MATH_FP32, the flag kernel and the per-step kernels "
              "do not offer it", 64 * kMaxC, 2 * HQ, cus);
+  VS_REQUIRE(!carry || (tagged && !gates_save && !c_save && !lengths && !rowbias),
+             "lstm: the carried state is served by the tagged persistent recurrence in eval mode alone (dims.math F16X3 or BF16, H <= %d, "
+             "2*H/8 = %d workgroups <= %d CUs, vs_set_lstm_kernel 0 or 2, no lengths, one speaker per mixture); VS_MATH_FP32, the flag kernel "
+             "and the per-step kernels start from a zero state", 64 * kMaxC, 2 * HQ, cus);
   if (tagged) VS_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(state + per), (int)kSentinel, 3 * per, stream));
+  if (carry && carry->state_in) {          // h_0 of the forward direction into exchange buffer 0 (zeroed above), in the kernel's operand form
+    const long long n = (long long)B * HQ;
+    if (math == VS_MATH_CODE_BF16)
+      hipLaunchKernelGGL((lstm16_seed_kernel<1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, carry->state_in, reinterpret_cast<u32x4_t*>(state), B, H);
+    else
+      hipLaunchKernelGGL((lstm16_seed_kernel<2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, carry->state_in, reinterpret_cast<u32x4_t*>(state), B, H);
+    VS_LAUNCH_CHECK();
+  }
   if (persistent) {
     unsigned* flags = reinterpret_cast<unsigned*>(state + 2 * per);      // zeroed above
     unsigned* err = reinterpret_cast<unsigned*>(state + 4 * per);         // first of the 64 trailing words
@@ -1493,7 +1594,8 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
           void* hb2 = state + 2 * per;
           void* hb3 = state + 3 * per;
           LstmSharedIn sh{rowbias, K};
-          void* params[] = {&a, &hb2, &hb3, &lengths, &sh};
+          LstmCarry cy{carry ? carry->state_in : nullptr, carry ? carry->state_out : nullptr, carry ? carry->keep : 0};
+          void* params[] = {&a, &hb2, &hb3, &lengths, &sh, &cy};
           const void* kernel = math == VS_MATH_CODE_BF16
               ? (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, false>))
               : (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, false>));
@@ -1501,6 +1603,9 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
             kernel = math == VS_MATH_CODE_BF16
                 ? (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, true, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, false, true>))
                 : (lengths ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, true, true>) : reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, false, true>));
+          if (carry)
+            kernel = math == VS_MATH_CODE_BF16 ? reinterpret_cast<const void*>(&lstm16_tagged_kernel<1, false, false, true>)
+                                               : reinterpret_cast<const void*>(&lstm16_tagged_kernel<2, false, false, true>);
           e = hipLaunchCooperativeKernel(kernel, dim3(HQ * nbt, 2), dim3(256), params, 0, stream);
         } else
         e = math == VS_MATH_CODE_BF16
@@ -1515,6 +1620,8 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
                    hipGetErrorString(e));
         VS_REQUIRE(!rowbias, "lstm: shared-input recurrence: the persistent recurrence could not be launched resident (%s) and the per-step kernels do not "
                    "offer it", hipGetErrorString(e));
+        VS_REQUIRE(!carry, "lstm: carried state: the persistent recurrence could not be launched resident (%s) and the per-step kernels start from "
+                   "a zero state", hipGetErrorString(e));
         launched = false;
         break;
       }

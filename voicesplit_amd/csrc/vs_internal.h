@@ -269,11 +269,19 @@ inline VsLstmBf16Layout vs_lstm_bf16_layout(long long M, int K, int H) {
 // math (VS_MATH_CODE_*): which products the persistent recurrences use -- fp32 MFMA, or (forward) split-f16 / f16 and
 // (BPTT, VS_MATH_BF16 only) bf16; the pack calls write the matching operand form behind the fp32 one
 int vs_lstm_pack_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
+struct VsLstmCarry {
+  const float* state_in;   // device [B][2][H] fp32 (h, then c) of the forward direction in front of frame 0, or NULL: zero
+  float* state_out;        // device [B][2][H] fp32: the same behind frame keep - 1
+  int keep;                // 1 <= keep <= T
+};
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
                              int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32,
                              const int* lengths = nullptr /* device [B]: h = c = 0 while t >= lengths[b]; only the tagged persistent kernel takes them */,
                              const float* rowbias = nullptr /* [B][8H]: the shared-input form, xg [B / K][T][8H] and lengths [B / K] (lstm.hip) */,
-                             int K = 1);
+                             int K = 1,
+                             const VsLstmCarry* carry = nullptr /* the carry form: forward direction from / to a caller-held state (lstm.hip) */);
+// the refusals of the carry form that need no device (argument ranges, arithmetic, hidden size, vs_set_lstm_kernel)
+int vs_lstm_carry_check(int math, int H, int T, int keep, const float* state_out, const char* what);
 int vs_lstm_pack_t_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
 int vs_bilstm_bwd_recurrent_impl(const float* wpt, float* state, float* gates, const float* c_all, const float* dout,
                                  int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32);

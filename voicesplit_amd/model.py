@@ -285,6 +285,26 @@ class _MaskNet(nn.Module):
 
         return conv_stage, sequence_stage
 
+    def stream_stages(self, want_logits: bool = False):
+        """(conv_stage, carry_stage, head_stage) for ``streaming.StreamingMasker``: the conv stack on a window of a stream, the
+        BiLSTM over [chunk | look-ahead] with its forward direction carried from chunk to chunk (``ops.bilstm_carry``) and the head
+        on the chunk's rows, all in eval mode, all straight into the C ABI stage entry points.  want_logits: the head stage
+        returns (mask, logits)."""
+        if self.training:
+            raise RuntimeError("stream separation runs in eval mode (BatchNorm running statistics, no tape): call model.eval() first")
+        sd = {k: v.detach() for k, v in self._tensors().items()}
+
+        def conv_stage(xw):
+            return ops.conv_stack(sd, xw.contiguous(), self._dims(xw.shape[0], xw.shape[1]), self.conv_act)
+
+        def carry_stage(feat, dvec, state, keep):
+            return ops.bilstm_carry(sd, feat.contiguous(), dvec.contiguous(), self._dims(feat.shape[0], feat.shape[1]), state, keep)
+
+        def head_stage(lstm_out):
+            return ops.head(sd, lstm_out.contiguous(), self._dims(lstm_out.shape[0], lstm_out.shape[1]), want_logits=want_logits)
+
+        return conv_stage, carry_stage, head_stage
+
     def forward_ragged(self, x, speaker_embedding, lengths):
         """A padded batch of clips of unequal length, each as if alone: x [B, Tmax, num_freq], lengths [B] (sequence or
         tensor, 1 <= lengths[b] <= Tmax) -> mask [B, Tmax, fc2_dim] whose rows t < lengths[b] are

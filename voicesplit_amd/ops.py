@@ -339,6 +339,37 @@ def bilstm_ragged(sd, feat, dvec, lengths, dims: VsDims, workspace=None) -> torc
     return bilstm(sd, feat, dvec, dims, workspace=workspace, lengths=lengths)
 
 
+def _check_carry_state(state, B: int, H: int, device):
+    if state is None:
+        return None
+    _dev_check(state, "state")
+    if tuple(state.shape) != (B, 2, H) or state.device != device:
+        raise ValueError(f"state must be [B, 2, H] = [{B}, 2, {H}] (h, then c) on {device}, got {tuple(state.shape)} on {state.device}")
+    if state.data_ptr() % 16:
+        raise ValueError("state must be 16-byte aligned (the kernels read it in float4 units)")
+    return state
+
+
+def bilstm_carry(sd, feat, dvec, dims: VsDims, state=None, keep: Optional[int] = None, workspace=None):
+    """The sequence stage over one chunk of a stream (vs_bilstm_fwd_carry): feat [B, T, 8F] = [chunk | look-ahead], the forward
+    direction continues from ``state`` [B, 2, H] (h, then c; None: zero, the stream's first chunk), the reverse direction starts
+    from zero at frame T - 1.  Returns (lstm_out [B, T, 2H], state behind frame keep - 1 [B, 2, H]); keep defaults to T."""
+    lib = _lib.load()
+    _dev_check(feat, "feat")
+    _dev_check(dvec, "speaker_embedding")
+    keep = dims.T if keep is None else int(keep)
+    state = _check_carry_state(state, dims.B, dims.H, feat.device)
+    params = pack_params(sd)
+    ws = workspace if workspace is not None else get_workspace(dims, feat.device)
+    out = torch.empty(dims.B, dims.T, 2 * dims.H, dtype=torch.float32, device=feat.device)
+    state_out = torch.empty(dims.B, 2, dims.H, dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device):
+        rc = lib.vs_bilstm_fwd_carry(ctypes.byref(dims), ctypes.byref(params), _p(feat), _p(dvec), _p(state), _p(state_out), keep,
+                                     _p(ws), ws.numel(), _p(out), _stream())
+    check(rc, "vs_bilstm_fwd_carry")
+    return out, state_out
+
+
 def zero_tail_rows(t: torch.Tensor, lengths) -> torch.Tensor:
     """In place: rows t[b, lengths[b]:] := 0 of a contiguous [B, T, ...] tensor (vs_zero_tail_rows; unit-test surface)."""
     lib = _lib.load()
@@ -470,6 +501,30 @@ def bilstm_recurrent(xg, w_hh_f, w_hh_b, math=None):
               "vs_bilstm_recurrent_math")
     _lstm_check_err(state, state.numel() - 64, "vs_bilstm_recurrent")
     return out
+
+
+def bilstm_recurrent_carry(xg, w_hh_f, w_hh_b, math, state=None, keep: Optional[int] = None):
+    """The raw carry recurrence (vs_bilstm_recurrent_carry): xg [B,T,8H] (bias already added), the forward direction from ``state``
+    [B,2,H] (h, then c; None: zero) -> (out [B,T,2H], state behind frame keep - 1 [B,2,H]); keep defaults to T.  math: MATH_F16X3 or
+    MATH_BF16 (code or name); everything else is refused by the library."""
+    lib = _lib.load()
+    for n, t in (("xg", xg), ("w_hh_f", w_hh_f), ("w_hh_b", w_hh_b)):
+        _dev_check(t, n)
+    math = MATH_CODES[math] if isinstance(math, str) else int(math)
+    B, T, H8 = xg.shape
+    H = H8 // 8
+    keep = T if keep is None else int(keep)
+    state_in = _check_carry_state(state, B, H, xg.device)
+    packed = torch.empty(lib.vs_lstm_packed_floats(H), dtype=torch.float32, device=xg.device)
+    scratch = torch.empty(lib.vs_lstm_state_floats(B, H), dtype=torch.float32, device=xg.device)
+    out = torch.empty(B, T, 2 * H, dtype=torch.float32, device=xg.device)
+    state_out = torch.empty(B, 2, H, dtype=torch.float32, device=xg.device)
+    with torch.cuda.device(xg.device):
+        check(lib.vs_lstm_pack_math(_p(w_hh_f), _p(w_hh_b), _p(packed), H, math, _stream()), "vs_lstm_pack_math")
+        check(lib.vs_bilstm_recurrent_carry(_p(xg), _p(packed), _p(scratch), _p(out), _p(state_in), _p(state_out), keep, B, T, H, math,
+                                            _stream()), "vs_bilstm_recurrent_carry")
+    _lstm_check_err(scratch, scratch.numel() - 64, "vs_bilstm_recurrent_carry")
+    return out, state_out
 
 
 def _lstm_check_err(state: torch.Tensor, word: int, what: str):

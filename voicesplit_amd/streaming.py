@@ -16,8 +16,15 @@ activation memory -- is windowed (halo >= 65: every kept frame sees its full rec
 edges are zero-padded exactly as the whole-clip convolution pads them), the stitched feature
 sequence then goes through the BiLSTM and the head ONCE at full length, so the recurrent state is
 carried across every window boundary in both directions by construction.
+
+``StreamingMasker`` is the live form: frames arrive a few at a time and mask rows leave a bounded number of frames later (the
+latency-controlled BiLSTM).  The conv stack is exact (every feature frame is computed once, from a window that gives it its full
+receptive field or ends at a true stream edge), the forward LSTM direction carries its state from chunk to chunk and so is the
+whole-stream recurrence, the reverse direction of a chunk of ``C`` frames starts from a zero state ``R`` look-ahead frames behind
+the chunk's end.  With ``C + R`` at least the stream length it is the plain forward.
 """
-from typing import Callable, List, Tuple
+from collections import namedtuple
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
@@ -188,3 +195,122 @@ def padded_frame_share(lengths, batches) -> float:
     lens = [int(n) for n in lengths]
     total = sum(len(b) * max(lens[i] for i in b) for b in batches)
     return 1.0 - sum(lens) / total if total else 0.0
+
+
+# ---- a stream, chunk by chunk ---------------------------------------------------------------------------------------------
+# feat_lo, feat_hi: the feature frames [feat_lo, feat_hi) that are finalised now; win_lo, win_hi: the input frames [win_lo, win_hi)
+# the conv stack runs on for that (empty when no feature frame is due); chunks: [(k, lo, hi, e)] emitted now, in order -- chunk k
+# keeps mask rows [lo, hi) and its recurrence runs over feature frames [lo, e)
+StreamPlan = namedtuple("StreamPlan", "feat_lo feat_hi win_lo win_hi chunks")
+
+
+def plan_stream(pushed: int, finished: bool, C: int, R: int, halo: int = CONV_RECEPTIVE_HALO,
+                feat_done: int = 0, chunks_done: int = 0) -> StreamPlan:
+    """What a stream of which ``pushed`` frames have arrived (``finished``: no more will) can do now, given that feature frames
+    [0, feat_done) are final and chunks [0, chunks_done) are out.  Pure host arithmetic.
+
+    Chunk k covers frames [kC, (k+1)C) and needs the features of [kC, (k+1)C + R); feature frame t is final once frame t + halo
+    has arrived, so chunk k is due at exactly (k+1)C + R + halo pushed frames.  At the end of the stream everything is clipped
+    to its length T = pushed and every remaining chunk is due.  Features are finalised when a chunk needs them, never twice:
+    [feat_done, e of the last due chunk), from a conv window that starts ``halo`` frames earlier (or at frame 0) and ends
+    ``halo`` frames later (or at the true end of the stream) -- always inside the stream, as in ``plan_windows_exact``."""
+    if C < 1 or R < 0 or halo < 0:
+        raise ValueError(f"plan_stream: C = {C} must be >= 1, R = {R} and halo = {halo} >= 0")
+    if pushed < 0 or not 0 <= feat_done <= pushed or chunks_done < 0 or chunks_done * C > feat_done:
+        raise ValueError(f"plan_stream: inconsistent state pushed = {pushed}, feat_done = {feat_done}, chunks_done = {chunks_done}")
+    due = -(-pushed // C) if finished else max(0, (pushed - R - halo) // C)
+    chunks = []
+    for k in range(chunks_done, due):
+        hi, e = (k + 1) * C, (k + 1) * C + R
+        chunks.append((k, k * C, min(hi, pushed), min(e, pushed)) if finished else (k, k * C, hi, e))
+    feat_hi = max(feat_done, chunks[-1][3]) if chunks else feat_done
+    if feat_hi == feat_done:
+        return StreamPlan(feat_done, feat_done, feat_done, feat_done, chunks)
+    return StreamPlan(feat_done, feat_hi, max(0, feat_done - halo), pushed if finished else feat_hi + halo, chunks)
+
+
+class StreamingMasker:
+    """Masks of ``B`` streams that advance in lockstep, emitted chunk by chunk.
+
+    ``conv_stage(x [B, Tw, F]) -> feat [B, Tw, Cf]`` is the eval-mode conv stack, ``carry_stage(feat [B, n, Cf], dvec [B, E],
+    state or None, keep) -> (lstm_out [B, n, 2H], state)`` the sequence stage whose forward direction starts from ``state``
+    (None: zero) and returns its state behind frame ``keep - 1``, ``head_stage(lstm_out [B, n, 2H]) -> mask [B, n, F2]`` (or
+    ``(mask, logits)``) the head.  ``VoiceSplit.stream_stages()`` returns the HIP ones.  The d-vectors are fixed for the life of
+    the object.  ``push(frames [B, n, F])`` returns the mask rows that became due, [B, m, F2] with m >= 0 a multiple of ``C``;
+    ``finish()`` returns the rest.  Kept between calls: the input frames the next conv window needs, the finalised features of the
+    chunks not yet out, the forward state.  ``trace=True`` keeps every chunk's ``lstm_out`` rows (and logits) in ``self.trace``.
+    """
+
+    def __init__(self, conv_stage: Callable, carry_stage: Callable, head_stage: Callable, dvec: torch.Tensor, C: int, R: int,
+                 halo: int = CONV_RECEPTIVE_HALO, trace: bool = False):
+        if dvec.dim() != 2:
+            raise ValueError(f"dvec must be [B, E], got {tuple(dvec.shape)}")
+        plan_stream(0, False, C, R, halo)                      # range checks
+        self.conv_stage, self.carry_stage, self.head_stage = conv_stage, carry_stage, head_stage
+        self.dvec = dvec.contiguous()
+        self.C, self.R, self.halo = int(C), int(R), int(halo)
+        self.pushed = self.feat_done = self.chunks_done = 0
+        self.finished = False
+        self.trace = [] if trace else None
+        self._x = None          # input frames [_x0, pushed)
+        self._x0 = 0
+        self._feat = None       # final features [_f0, feat_done)
+        self._f0 = 0
+        self._state = None
+        self._out_dim = None
+
+    @property
+    def latency_frames(self) -> int:
+        """Mask row t is returned by the push that brings the number of pushed frames to (t // C + 1) * C + R + halo <= t +
+        latency_frames, or by ``finish()``."""
+        return self.C + self.R + self.halo
+
+    @property
+    def emitted(self) -> int:
+        return min(self.chunks_done * self.C, self.pushed)
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("StreamingMasker: the stream has been finished")
+        if frames.dim() != 3 or frames.shape[0] != self.dvec.shape[0]:
+            raise ValueError(f"frames must be [B = {self.dvec.shape[0]}, n, F], got {tuple(frames.shape)}")
+        if self._x is not None and frames.shape[2] != self._x.shape[2]:
+            raise ValueError(f"frames have {frames.shape[2]} bins, the stream has {self._x.shape[2]}")
+        self._x = frames if self._x is None else torch.cat((self._x, frames), dim=1)
+        self.pushed += frames.shape[1]
+        return self._advance()
+
+    def finish(self) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("StreamingMasker: the stream has been finished")
+        if self._x is None:
+            raise RuntimeError("StreamingMasker: finish() on a stream that never received a frame")
+        self.finished = True
+        return self._advance()
+
+    def _advance(self) -> torch.Tensor:
+        plan = plan_stream(self.pushed, self.finished, self.C, self.R, self.halo, self.feat_done, self.chunks_done)
+        pieces = []
+        with torch.no_grad():
+            if plan.feat_hi > plan.feat_lo:
+                window = self._x[:, plan.win_lo - self._x0:plan.win_hi - self._x0].contiguous()
+                new = self.conv_stage(window)[:, plan.feat_lo - plan.win_lo:plan.feat_hi - plan.win_lo]
+                self._feat = new if self._feat is None or self._feat.shape[1] == 0 else torch.cat((self._feat, new), dim=1)
+                self.feat_done = plan.feat_hi
+                keep_from = max(0, self.feat_done - self.halo)          # left edge of the next conv window
+                self._x, self._x0 = self._x[:, keep_from - self._x0:], keep_from
+            for k, lo, hi, e in plan.chunks:
+                seg = self._feat[:, lo - self._f0:e - self._f0].contiguous()
+                lstm_out, self._state = self.carry_stage(seg, self.dvec, self._state, hi - lo)
+                rows = lstm_out[:, :hi - lo].contiguous()
+                out = self.head_stage(rows)
+                mask, logits = out if isinstance(out, tuple) else (out, None)
+                if self.trace is not None:
+                    self.trace.append({"chunk": k, "lo": lo, "hi": hi, "e": e, "lstm_out": rows, "logits": logits})
+                pieces.append(mask)
+                self._out_dim = mask.shape[2]
+                self._feat, self._f0 = self._feat[:, hi - self._f0:], hi
+                self.chunks_done = k + 1
+        if pieces:
+            return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
+        return self._x.new_empty(self._x.shape[0], 0, self._out_dim if self._out_dim is not None else self._x.shape[2])
