@@ -199,7 +199,7 @@ int vs_head_fwd(const vs_dims* dims, const vs_params* params, const float* lstm_
  *     recurrence holds h = c = 0 while t >= lengths[b], in both directions;
  *   head: runs over all B*T rows, then the mask's tail rows are zeroed.
  * Eval mode only (BatchNorm running statistics), dims.math = VS_MATH_F16X3 or VS_MATH_BF16; VS_MATH_FP32 and a
- * recurrence other than the tagged persistent kernel (H > 448, a grid that is not resident, vs_set_lstm_kernel != 0)
+ * recurrence other than the tagged persistent kernel (H > 448, a grid that is not resident, a vs_set_lstm_kernel mode other than 0 or 2)
  * are refused with an error, never computed some other way.  workspace: vs_workspace_bytes(dims), as for B x T. */
 int vs_forward_prepared_ragged(const vs_dims* dims, const vs_params* params, const void* prepared, size_t prepared_bytes,
                                const float* x, const float* dvec, const int* lengths, int conv_act,

@@ -29,7 +29,7 @@ class _RoundSTE(torch.autograd.Function):
 
 
 class _RecurrentProduct(torch.autograd.Function):
-    """h_{t-1} @ W_hh^T as the VS_MATH_BF16 recurrence computes it (csrc/lstm.hip, lstm16_*): forward operands rounded
+    """h_{t-1} @ W_hh^T as the VS_MATH_BF16 recurrence computes it (csrc/lstm_fwd.hip and lstm_bwd.hip, lstm16_*): forward operands rounded
     to f16, the BPTT's product W_hh^T @ dgates and the dW_hh contraction on bf16-rounded operands."""
 
     @staticmethod

@@ -1,4 +1,4 @@
-"""The BiLSTM recurrence / BPTT with the recurrent products on the f16 / bf16 matrix instructions (csrc/lstm.hip,
+"""The BiLSTM recurrence / BPTT with the recurrent products on the f16 / bf16 matrix instructions (csrc/lstm_fwd.hip, csrc/lstm_bwd.hip,
 lstm16_*: what dims.math = VS_MATH_F16X3 / VS_MATH_BF16 select) against autograd through the explicit recurrence in
 fp64 (nn.LSTM of models/voicesplit/model.py:57-61,82 and its backward under train.py:110).
 

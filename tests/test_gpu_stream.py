@@ -1,4 +1,4 @@
-"""GPU: stream separation chunk by chunk -- the carry mode of the tagged persistent recurrence (csrc/lstm.hip), the sequence stage
+"""GPU: stream separation chunk by chunk -- the carry mode of the tagged persistent recurrence (csrc/lstm_fwd.hip), the sequence stage
 built on it, streaming.StreamingMasker on the HIP stages and audio.StreamingSeparator, in both arithmetics.
 
 Oracles are fp64: an explicit recurrence with an initial state for the raw kernel; ``oracle.reference_forward.forward`` of the

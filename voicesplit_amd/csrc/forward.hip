@@ -542,7 +542,7 @@ int bilstm(const Fwd& f, const float* feat, const float* dvec, float* lstm_out, 
     }
     // both directions in one launch (N = 8H): twice the workgroups, half the tail quantisation.  multi: the K speakers of a mixture
     // share its gate pre-activations, so the big GEMM runs once per mixture WITHOUT the row bias; the shared-input recurrence adds each
-    // sequence's own (lstm.hip).  The conv stack is done: its activation ping-pong is the GEMM's operand scratch (feat may be the
+    // sequence's own (lstm_fwd.hip).  The conv stack is done: its activation ping-pong is the GEMM's operand scratch (feat may be the
     // caller's own buffer) -- the second buffer where cnn8 left the A operand, else both.
     VsLstmGemmReady ready;
     if (f.prep) { ready.wscale2 = f.prep->gemm_wscale; ready.wh = f.prep->wih_hi; ready.wl = f.prep->wih_lo; }

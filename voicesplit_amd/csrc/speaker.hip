@@ -30,7 +30,7 @@ namespace {
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 constexpr int kMaxLayers = 4;
-constexpr float kHScale = 1024.f;      // h is exchanged as f16(h * 2^10) + f16(remainder), as in lstm.hip
+constexpr float kHScale = 1024.f;      // h is exchanged as f16(h * 2^10) + f16(remainder), as in lstm_fwd.hip
 
 struct SpkShape {
   int M, H, L, E, W, S, math;

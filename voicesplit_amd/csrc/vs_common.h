@@ -67,7 +67,7 @@ __device__ __forceinline__ float vs_sigmoid(float x) { return 1.0f / (1.0f + exp
 // ocml tanhf: accurate near 0 (a (1-e)/(1+e) form cancels there)
 __device__ __forceinline__ float vs_tanh(float x) { return tanhf(x); }
 
-// The recurrence's gate arithmetic sits on the step-to-step critical path of ONE wave (lstm.hip): 12 sigmoids and
+// The recurrence's gate arithmetic sits on the step-to-step critical path of ONE wave (lstm_fwd.hip): 12 sigmoids and
 // 8 tanh per lane and step.  The ocml forms (expf + IEEE divide, tanhf) are ~20-25 dependent VALU each -- ~1 us per
 // step for a lone wave; these are 4 and 12: v_exp_f32 / v_rcp_f32 (1 ulp each).  sigmoid: <= ~3e-7 relative.  tanh: the
 // 1 - 2/(1+e^2x) form cancels near 0 (absolute error one ulp of 1), so |x| < 1/8 takes the odd series up to x^7

@@ -265,7 +265,7 @@ inline VsLstmBf16Layout vs_lstm_bf16_layout(long long M, int K, int H) {
   L.total = L.dxg + align_up((size_t)M * 8 * H * 2);
   return L;
 }
-// lstm.hip
+// lstm_fwd.hip (forward recurrence, vs_set_lstm_kernel) and lstm_bwd.hip (BPTT)
 // math (VS_MATH_CODE_*): which products the persistent recurrences use -- fp32 MFMA, or (forward) split-f16 / f16 and
 // (BPTT, VS_MATH_BF16 only) bf16; the pack calls write the matching operand form behind the fp32 one
 int vs_lstm_pack_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
@@ -277,11 +277,15 @@ struct VsLstmCarry {
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
                              int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32,
                              const int* lengths = nullptr /* device [B]: h = c = 0 while t >= lengths[b]; only the tagged persistent kernel takes them */,
-                             const float* rowbias = nullptr /* [B][8H]: the shared-input form, xg [B / K][T][8H] and lengths [B / K] (lstm.hip) */,
+                             const float* rowbias = nullptr /* [B][8H]: the shared-input form, xg [B / K][T][8H] and lengths [B / K] (lstm_fwd.hip) */,
                              int K = 1,
-                             const VsLstmCarry* carry = nullptr /* the carry form: forward direction from / to a caller-held state (lstm.hip) */);
+                             const VsLstmCarry* carry = nullptr /* the carry form: forward direction from / to a caller-held state (lstm_fwd.hip) */);
 // the refusals of the carry form that need no device (argument ranges, arithmetic, hidden size, vs_set_lstm_kernel)
 int vs_lstm_carry_check(int math, int H, int T, int keep, const float* state_out, const char* what);
+// what vs_set_lstm_kernel last set (the one copy of the mode lives in lstm_fwd.hip)
+int vs_lstm_kernel_mode();
+// behind a persistent launch: when its error word is set (a spin gave up), NaN into the first min(n, 64) floats of the n in `out`
+int vs_lstm_poison_impl(const unsigned* err, float* out, long long n, hipStream_t);
 int vs_lstm_pack_t_impl(const float*, const float*, float*, int, hipStream_t, int math = VS_MATH_CODE_FP32);
 int vs_bilstm_bwd_recurrent_impl(const float* wpt, float* state, float* gates, const float* c_all, const float* dout,
                                  int B, int T, int H, hipStream_t, int math = VS_MATH_CODE_FP32);
