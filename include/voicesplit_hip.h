@@ -779,6 +779,38 @@ size_t vs_logmel_workspace_bytes(const vs_loss_dims* dims, long long n, int n_me
 int vs_wav_to_logmel(const vs_loss_dims* dims, const float* wav, long long n, const float* mel_basis, int n_mels, float* mel,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* =============================================================================================
+ * ABI 11 (additive entries).  Training mixtures from a pool of clean utterances resident on the device: the arithmetic of mix_wavfiles
+ * (utils/generic_utils.py:300-345: librosa.effects.trim(top_db=20), crop to audio_len, add, divide by 1.1 max|mixed|).
+ * The pool is ONE flat fp32 buffer of `total` samples, 16-byte aligned; clip i is samples[offsets[i] : offsets[i+1]].
+ *
+ * vs_trim_bounds: bounds[i] = (start, end) of librosa.effects.trim(y, top_db=20) with its defaults frame_length = 2048,
+ * hop_length = 512, ref = np.max (librosa 0.7: centred frames, reflect padding), defined as
+ *   yp     = y (n samples) padded by 1024 samples on each side by reflection without the edge sample
+ *   mse[f] = mean(yp[512 f : 512 f + 2048]^2), f = 0 .. n / 512
+ *   frame f is non-silent when max(1e-10, mse[f]) / max(1e-10, max_f mse[f]) > 1e-2
+ *   start  = 512 * first non-silent f, end = min(n, 512 * (last non-silent f + 1)); (0, 0) without one
+ * (an all-zero clip has every frame at the clamp: ratio 1, bounds (0, n)).  Sums in fp64.  peak, when not NULL: [N] fp32,
+ * max |y| over [start, end).  The padding reflects at the clip's own ends: a neighbouring clip is never read.
+ * offsets: [N + 1] int64 on the device; offsets_host: the same values in HOST memory (the one host pointer of this ABI), checked
+ * here before anything is launched: a clip shorter than 1025 samples (the reflection would wrap) or longer than 2^30 is refused
+ * with -1 and a message.  workspace: vs_trim_workspace_bytes(total, N) bytes, 256-byte aligned.  One launch, a workgroup per clip.
+ * ============================================================================================= */
+size_t vs_trim_workspace_bytes(long long total, int N);
+int vs_trim_bounds(const float* samples, long long total, const long long* offsets_host, const long long* offsets, int N,
+                   int* bounds, float* peak, void* workspace, size_t workspace_bytes, void* stream);
+/* One batch of mixtures.  clean_at, interf_at: [B] int64 on the device, the index in the flat buffer of each item's first sample
+ * (clip offset + trim start + crop offset; any alignment).  Per item b, with c = samples[clean_at[b] : + L], i = samples[interf_at[b] : + L]:
+ *   m = max_j |c[j] + i[j]| (sum in fp32),  norm[b] = float(1.1 * double(m)),
+ *   mixed_wav[b] = (c + i) / norm,  target_wav[b] = c / norm   (IEEE fp32 division)
+ * m == 0 (the reference divides by zero there): valid[b] = 0 and both rows are zero; otherwise valid[b] = 1.  An index outside
+ * [0, total - L] is not read: valid[b] = -1, rows of zeros.  invalid_count, when not NULL: one int32 on the device, incremented
+ * once per item with valid != 1 (never cleared here).  mixed_wav, target_wav [B][L] (16-byte aligned), norm [B], valid [B] int32.
+ * 1 <= B <= 65535.  The maximum is order-independent: two calls give the same bits.  Four launches on `stream` (norm doubles as the
+ * maximum's slot and is cleared first); nothing is allocated, no environment variable is read. */
+int vs_mix_clips(const float* samples, long long total, const long long* clean_at, const long long* interf_at, int B, int L,
+                 float* mixed_wav, float* target_wav, float* norm, int* valid, int* invalid_count, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

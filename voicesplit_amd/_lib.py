@@ -219,6 +219,10 @@ SIGNATURES = {
     "vs_speaker_embed": (c_int, [POINTER(VsSpeakerDims), _P, c_size_t, _P, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "vs_logmel_workspace_bytes": (c_size_t, [POINTER(VsLossDims), c_longlong, c_int]),
     "vs_wav_to_logmel": (c_int, [POINTER(VsLossDims), _P, c_longlong, _P, c_int, _P, _P, c_size_t, _P]),
+    # training mixtures from a resident pool of clean utterances
+    "vs_trim_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "vs_trim_bounds": (c_int, [_P, c_longlong, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "vs_mix_clips": (c_int, [_P, c_longlong, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -702,6 +702,41 @@ def synthetic_batches(steps: int, B: int, T: int, F: int, E: int, hop: int, devi
         yield emb, target, mixed, seq_len, None, phase
 
 
+def _mixture_batches(args, c, acfg, b, rank, world, dev):
+    """``--mix-csv``: the clean corpus resident on this rank's GPU and a ``mixing.MixtureBatches`` over the CSV's triplets."""
+    from . import mixing
+    paths, triplets, numbers, skipped = mixing.read_triplet_csv(args.mix_csv, args.mix_root, args.librispeech)
+    if not triplets:
+        raise ValueError(f"{args.mix_csv}: no triplet with all three files under {args.mix_root}")
+    pool = mixing.ClipPool.from_files(paths, int(acfg["sample_rate"]), dev)
+    L = mixing.samples_for(acfg, c.audio["audio_len"])
+    if args.emb_dir:
+        embs = [torch.load(os.path.join(args.emb_dir, "%06d-emb.pt" % n)) for n in numbers]
+        has = [e.tolist() != [0] for e in embs]                                 # utils/dataset.py:93-95
+        triplets = [t for t, h in zip(triplets, has) if h]
+        embs = [e.float().reshape(-1) for e, h in zip(embs, has) if h]
+        keep = mixing.keep_mask(pool, triplets, L)
+        kept = [t for t, k in zip(triplets, keep) if k]
+        table, rows = torch.stack([e for e, k in zip(embs, keep) if k]).to(dev), "triplet"
+    else:
+        if not args.speaker_checkpoint:
+            raise ValueError("--mix-csv needs --emb-dir or --speaker-checkpoint")
+        from .speaker import SpeakerEncoder
+        enc = SpeakerEncoder(num_mels=int(acfg.get("num_mels", 40)))
+        enc.load_state_dict(torch.load(args.speaker_checkpoint, map_location="cpu"), strict=True)
+        refs = sorted({t[1] for t in triplets})
+        table = torch.zeros(len(pool), enc.emb_dim, device=dev)
+        table[torch.tensor(refs, device=dev)] = pool.embed(enc.eval().to(dev), acfg, refs)
+        kept, _ = mixing.plan_triplets(pool, triplets, L, emb_ok=(table.abs().sum(dim=1) > 0).tolist())
+        rows = "clip"
+    if rank == 0:
+        print(f"{len(kept)} triplets from {len(pool)} clips ({pool.total / acfg['sample_rate'] / 3600:.2f} h on the device); "
+              f"{len(numbers) - len(kept)} dropped (too short, silent or without an embedding), {skipped} skipped for a missing file", flush=True)
+    shard = EpochShard(len(kept), b, rank, world, c.train_config["seed"])
+    return mixing.MixtureBatches(pool, kept, table, acfg, c.audio["audio_len"], shard, crop=args.mix_crop,
+                                 seed=c.train_config["seed"], emb_rows=rows)
+
+
 def main(argv=None):
     """``python -m torch.distributed.run --nproc-per-node N -m voicesplit_amd.trainer -c config.json``
     (train.py's CLI: --config_path/-c, --checkpoint_path; plus --synthetic-steps for a dry run)."""
@@ -713,6 +748,13 @@ def main(argv=None):
     ap.add_argument("--checkpoint_path", default=None)
     ap.add_argument("--synthetic-steps", type=int, default=0, help="train on random batches of the configured shape instead of c.dataset")
     ap.add_argument("--epochs", type=int, default=None)
+    ap.add_argument("--mix-csv", default=None, help="train from clean utterances: a triplet CSV [clean,embedding,interference]; "
+                    "the mixtures are made on the GPU (voicesplit_amd.mixing) instead of read from c.dataset")
+    ap.add_argument("--mix-root", default=".", help="directory the CSV's names are relative to")
+    ap.add_argument("--librispeech", action="store_true", help="the CSV holds LibriSpeech utterance ids (preprocess_by_csv.py -l)")
+    ap.add_argument("--mix-crop", choices=("head", "random"), default="head", help="head: the reference's [:audio_len]; random: a fresh crop every epoch")
+    ap.add_argument("--emb-dir", default=None, help="precomputed %%06d-emb.pt per CSV row, instead of embedding the reference clips here")
+    ap.add_argument("--speaker-checkpoint", default=None, help="embedder.pt of the GE2E speaker encoder (--mix-csv without --emb-dir)")
     args = ap.parse_args(argv)
     c = load_config(args.config_path)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -743,6 +785,8 @@ def main(argv=None):
         T = 1 + (int(c.audio["audio_len"]) * acfg["sample_rate"]) // acfg["hop_length"]
         batches = lambda e: synthetic_batches(args.synthetic_steps, b, T, acfg["num_freq"], c.model["emb_dim"],
                                               acfg["hop_length"], dev, seed=1000 * e + rank)
+    elif args.mix_csv:
+        batches = _mixture_batches(args, c, acfg, b, rank, world, dev).epoch
     else:
         ds = SpecWavDataset(c, train=True)
         shard = EpochShard(len(ds), b, rank, world, c.train_config["seed"])
