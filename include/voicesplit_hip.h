@@ -704,6 +704,24 @@ int vs_wav_to_spec(const vs_loss_dims* dims, const float* wav, float* spec, floa
  * (utils/audio_processor.py:478-491; est_mask*mixed_spec from utils/generic_utils.py:496).  mask may be NULL. */
 int vs_spec_to_wav(const vs_loss_dims* dims, const float* spec, const float* mask, const float* phase, float* wav,
                    void* workspace, size_t workspace_bytes, void* stream);
+/* The other branch of ap.inv_spectrogram (no phase given): Griffin-Lim, utils/audio_processor.py:492-496 and 516-523, with the
+ * conventions of the two calls above (periodic Hann, reflect padding, centre trimming).
+ *   S = (db_to_amp(denormalize(spec * mask) + ref_level_db)) ** power            (mask may be NULL)
+ *   y = istft(S * exp(i * init_phase));  n_iter times:  D = stft(y),  y = istft(S * D / |D|)
+ * A bin with |D| == 0 takes phase 0 (np.angle(0) == 0).  n_iter == 0 is the plain inverse.  init_phase [B][T][F] is required: random
+ * starting angles are the caller's to draw.  wav [B][hop*(T-1)].  residual (may be NULL): [n_iter][B] doubles on the device,
+ * residual[i][b] = || |D_i| - S ||_2 / || S ||_2 over item b, D_i = the STFT taken in iteration i (of the waveform entering it):
+ * Griffin-Lim's own objective, non-increasing in exact arithmetic.  The waveform path uses no floating-point atomics (wav is
+ * bit-identical across reruns); residual is summed with fp64 atomics (last bits may differ).  No host synchronisation, allocation or
+ * copy inside the call; five launches per iteration (six with vs_set_griffin_lim_reframe(1)). */
+size_t vs_griffin_lim_workspace_bytes(const vs_loss_dims* dims);
+int vs_griffin_lim(const vs_loss_dims* dims, const float* spec, const float* mask, const float* init_phase, float power, int n_iter,
+                   float* wav, double* residual, void* workspace, size_t workspace_bytes, void* stream);
+/* How an iteration of vs_griffin_lim turns the frames of one inverse into the windowed frames of the next transform: 1 = the
+ * overlap-add and framing kernels of the two calls above (through the waveform), 2 = one gather launch (every frame sample sums its
+ * <= ceil(win/hop) source frames itself), 0 = the default (the gather form: one launch fewer; not yet measured against the other, tools/griffin_lim_time.py).  Same
+ * sums in the same order: bit-identical results.  Process-wide, like vs_set_option.  Returns 0, or -1 for any other value. */
+int vs_set_griffin_lim_reframe(int mode);
 
 /* =============================================================================================
  * Evaluation metric: single-source BSS-eval SDR, the number the reference reports for every test item

@@ -207,6 +207,9 @@ SIGNATURES = {
     "vs_audio_workspace_bytes": (c_size_t, [POINTER(VsLossDims)]),
     "vs_wav_to_spec": (c_int, [POINTER(VsLossDims), _P, _P, _P, _P, c_size_t, _P]),
     "vs_spec_to_wav": (c_int, [POINTER(VsLossDims), _P, _P, _P, _P, _P, c_size_t, _P]),
+    "vs_griffin_lim_workspace_bytes": (c_size_t, [POINTER(VsLossDims)]),
+    "vs_griffin_lim": (c_int, [POINTER(VsLossDims), _P, _P, _P, c_float, c_int, _P, _P, _P, c_size_t, _P]),
+    "vs_set_griffin_lim_reframe": (c_int, [c_int]),
     "vs_sigmoid_bwd": (c_int, [_P, _P, _P, c_longlong, _P]),
     "vs_colsum": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     # evaluation metric

@@ -9,6 +9,7 @@ as calls into libvoicesplit_hip.so: the STFT / iSTFT run as one GEMM against a w
 plus a gather (the analysis window is 400 of the 1200 frame samples, so the dense basis is small).
 """
 import ctypes
+import math
 
 import torch
 
@@ -19,11 +20,11 @@ from .ops import _dev_check, _p, _stream
 _WS = {}
 
 
-def _workspace(d, device):
+def _workspace(d, device, sizer="vs_audio_workspace_bytes"):
     lib = _lib.load()
-    n = lib.vs_audio_workspace_bytes(ctypes.byref(d))
+    n = getattr(lib, sizer)(ctypes.byref(d))
     if n == 0:
-        _lib.check(-1, "vs_audio_workspace_bytes")
+        _lib.check(-1, sizer)
     key = torch.device(device).index
     ws = _WS.get(key)
     if ws is None or ws.numel() < n:
@@ -57,8 +58,13 @@ def wav_to_spec(wav: torch.Tensor, audio_cfg, want_phase: bool = True):
     return spec, phase
 
 
-def spec_to_wav(spec: torch.Tensor, phase: torch.Tensor, audio_cfg, mask: torch.Tensor = None) -> torch.Tensor:
-    """(spec * mask), phase [B,T,F] -> wav [B, hop*(T-1)] (ap.inv_spectrogram with the given phase)."""
+def spec_to_wav(spec: torch.Tensor, phase: torch.Tensor = None, audio_cfg=None, mask: torch.Tensor = None) -> torch.Tensor:
+    """(spec * mask), phase [B,T,F] -> wav [B, hop*(T-1)] (ap.inv_spectrogram with the given phase).  phase=None is the
+    reference's ``ap.inv_spectrogram(spec)``: ``griffin_lim`` with the config's ``power`` and ``griffin_lim_iters``."""
+    if audio_cfg is None:
+        raise TypeError("spec_to_wav: audio_cfg is required")
+    if phase is None:
+        return griffin_lim(spec, audio_cfg, mask=mask)
     lib = _lib.load()
     for n, t in (("spec", spec), ("phase", phase)):
         _dev_check(t, n)
@@ -74,12 +80,45 @@ def spec_to_wav(spec: torch.Tensor, phase: torch.Tensor, audio_cfg, mask: torch.
     return wav
 
 
-def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg) -> torch.Tensor:
+def griffin_lim(spec: torch.Tensor, audio_cfg, n_iter: int = None, power: float = None, init_phase: torch.Tensor = None,
+                mask: torch.Tensor = None, generator: torch.Generator = None, return_residual: bool = False):
+    """(spec * mask) [B,T,F] -> wav [B, hop*(T-1)] without a phase: ``_griffin_lim(S**power)`` of utils/audio_processor.py:492-496,
+    516-523 in one resident loop on the device (vs_griffin_lim).  n_iter / power default to ``audio_cfg["griffin_lim_iters"]`` /
+    ``audio_cfg["power"]``; init_phase=None draws ``2*pi*torch.rand`` on the device from ``generator`` (the reference's
+    ``np.random.rand`` angles).  Started from a mixture's phase with power=1 it is the consistency refinement of a masked
+    spectrogram.  return_residual: also ``|| |stft(y_i)| - S || / || S ||`` per iteration and item, fp64 [n_iter, B]."""
+    lib = _lib.load()
+    _dev_check(spec, "spec")
+    if mask is not None:
+        _dev_check(mask, "mask")
+    n_iter = int(audio_cfg["griffin_lim_iters"] if n_iter is None else n_iter)
+    power = float(audio_cfg["power"] if power is None else power)
+    if init_phase is None:
+        init_phase = 2.0 * math.pi * torch.rand(spec.shape, device=spec.device, dtype=torch.float32, generator=generator)
+    _dev_check(init_phase, "init_phase")
+    if init_phase.shape != spec.shape or (mask is not None and mask.shape != spec.shape):
+        raise ValueError(f"init_phase / mask must have the shape of spec {tuple(spec.shape)}")
+    B, T, F = spec.shape
+    d = loss_dims(B, T, F, audio_cfg)
+    ws = _workspace(d, spec.device, "vs_griffin_lim_workspace_bytes")
+    wav = torch.empty(B, d.hop * (T - 1), device=spec.device)
+    res = torch.empty(max(n_iter, 0), B, dtype=torch.float64, device=spec.device) if return_residual else None
+    with torch.cuda.device(spec.device):
+        rc = lib.vs_griffin_lim(ctypes.byref(d), _p(spec), _p(mask), _p(init_phase), power, n_iter, _p(wav), _p(res),
+                                _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "vs_griffin_lim")
+    return (wav, res) if return_residual else wav
+
+
+def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg, refine_iters: int = 0) -> torch.Tensor:
     """Target-speaker waveform for a batch of 3 s mixtures, all on the device:
-    wav [B, hop*(T-1)], dvec [B, emb_dim] -> est_wav [B, hop*(T-1)]   (test.py's loop body)."""
+    wav [B, hop*(T-1)], dvec [B, emb_dim] -> est_wav [B, hop*(T-1)]   (test.py's loop body).  refine_iters > 0: that many
+    Griffin-Lim rounds on the masked spectrogram, started from the mixture's phase (``griffin_lim`` with power 1)."""
     spec, phase = wav_to_spec(wav, audio_cfg)
     with torch.no_grad():
         mask = model(spec, dvec)
+    if refine_iters > 0:
+        return griffin_lim(spec, audio_cfg, n_iter=refine_iters, power=1.0, init_phase=phase, mask=mask)
     return spec_to_wav(spec, phase, audio_cfg, mask=mask)
 
 
