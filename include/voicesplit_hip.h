@@ -829,6 +829,56 @@ int vs_trim_bounds(const float* samples, long long total, const long long* offse
 int vs_mix_clips(const float* samples, long long total, const long long* clean_at, const long long* interf_at, int B, int L,
                  float* mixed_wav, float* target_wav, float* norm, int* valid, int* invalid_count, void* stream);
 
+/* =============================================================================================
+ * ABI 11 (additive entries).  Sample-rate conversion on the device: what librosa.load(path, sr=...) does on the CPU in front of
+ * mix_wavfiles and of both audio processors' load_wav.  The filter is a Kaiser-windowed sinc with the constants of resampy's
+ * kaiser_best AS REMEMBERED, its window evaluated analytically and not through resampy's interpolated table: RESTATED, NOT
+ * COMPARED WITH A RESAMPY OR LIBROSA RUN (neither is available where this was written).  This text is the contract.
+ *
+ * For integer rates sr_in, sr_out:  g = gcd,  L = sr_out / g,  M = sr_in / g,  s = min(1, L / M),
+ *   Z = 64,  H = ceil(Z / s),  T = 2 H + 1 taps,  beta = 14.769656459379492,  rho = 0.9475937167399596
+ *   h(t)  = rho sinc(rho t) I0(beta sqrt(1 - (t / Z)^2)) / I0(beta)   for |t| < Z, else 0        (sinc(x) = sin(pi x) / (pi x))
+ *   n_out = ceil(n_in L / M)                                                                      (librosa.load's fix_length)
+ *   y[n]  = sum_{j = -H .. H}  s h(s (r / L - j)) x[b + j],   b = floor(n M / L),  r = (n M) mod L,  x[k] = 0 outside [0, n_in)
+ * with n M in 64 bits.  The taps are a polyphase bank, bank[r][j + H] (L rows of T fp32), each tap evaluated in fp64 (the I0 series
+ * included) and rounded once to fp32.  sr_in == sr_out is a copy: L = M = 1, H = 0, T = 1, the one tap 1.0.  A pair of rates with
+ * L T 4 > 4 MiB is refused (16000 <-> 44101, for example); the pairs in use need at most 230 KB.
+ *
+ * POSITION INDEPENDENCE: y[n] = fmaf(tap[T-1], x[b+H], ... fmaf(tap[0], x[b-H], +0)), one fp32 chain in ascending j: its bits are
+ * a function of n and of the T samples it reads, never of the tile, workgroup, row, clip, window or call that computed it.  A stream
+ * resampled in pieces is therefore bit-identical to the stream resampled at once.
+ *
+ * vs_resample_plan: host only, no device.  Fills *dims (tile_periods and lds_bytes describe the launch, see csrc/resample.hip;
+ * tile_periods == 0: the direct kernel); -1 and a message for non-positive rates and refused pairs.  Every other call checks the
+ * dims it is given against a plan of its own.  vs_resample_out_len: ceil(n_in L / M), -1 for n_in < 0.
+ * vs_resample_bank: fills bank (dims->bank_bytes bytes, 16-byte aligned, device) on `stream`; once per pair of rates.
+ * ============================================================================================= */
+typedef struct vs_resample_dims {
+  int sr_in, sr_out;
+  int L, M, H, T;
+  int tile_periods;      /* periods (L outputs from M inputs) one workgroup owns */
+  int lds_bytes;         /* of that workgroup */
+  size_t bank_bytes;     /* L * T * 4 */
+} vs_resample_dims;
+int vs_resample_plan(int sr_in, int sr_out, vs_resample_dims* dims);
+long long vs_resample_out_len(const vs_resample_dims* dims, long long n_in);
+int vs_resample_bank(const vs_resample_dims* dims, float* bank, void* stream);
+/* Outputs [y_first, y_first + y_count) of B streams.  x: row b at x + b * x_stride holds stream samples [x_first, x_first + x_count)
+ * (x_first may be negative: the samples in front of the stream are zero anyway); y: row b at y + b * y_stride receives y_count
+ * outputs.  stream_len: the stream's length, or -1 while its end is not known; samples outside [0, stream_len) are zero.  An
+ * output that needs a sample inside the stream but outside the buffer is refused here, on the host (-1 and a message): the
+ * kernels read nothing outside [x_first, x_first + x_count).  With stream_len >= 0, y_first + y_count <= ceil(stream_len L / M).
+ * 1 <= B <= 65535, y_count >= 0 (0: nothing is launched).  Any alignment; rows are stored 16 bytes per lane where y allows it. */
+int vs_resample(const vs_resample_dims* dims, const float* bank, const float* x, long long x_first, long long x_count,
+                long long x_stride, long long stream_len, float* y, long long y_first, long long y_count, long long y_stride,
+                int B, void* stream);
+/* N clips of unequal length in flat buffers (the pool's layout), one launch sequence on `stream` for all of them.  clips [N][3]
+ * int64 on the device, clips_host the same values in HOST memory (checked here before anything is launched): clip i is
+ * in[c[0] : c[0] + c[1]] and its ceil(c[1] L / M) outputs go to out[c[2] : ...].  Any alignment; nothing outside a clip is read and
+ * nothing outside its outputs is written.  Clips of no samples are allowed.  The output regions must not overlap (not checked). */
+int vs_resample_clips(const vs_resample_dims* dims, const float* bank, const float* in, long long in_total, float* out,
+                      long long out_total, const long long* clips_host, const long long* clips, int N, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -10,6 +10,8 @@ Public surface (mirrors the reference):
   (utils/generic_utils.py:560-573).
 * ``SpeakerEncoder`` / ``logmel`` / ``mel_filterbank``: the GE2E speaker encoder that turns reference audio into the
   d-vector (notebooks/GE2E-Seungwonpark-ExtractSpeakerEmbedding-...py), ``voicesplit_amd/speaker.py``.
+* ``resample.Resampler`` / ``resample.StreamingResampler`` / ``audio.resample``: sample-rate conversion on the device, the
+  reference's ``librosa.load(path, sr=sample_rate)`` (``voicesplit_amd/resample.py``).
 * ``ops``: stage-level entry points over the C ABI of ``libvoicesplit_hip.so``.
 
 The compute path is the HIP library only; there is no PyTorch/CPU fallback.

@@ -63,6 +63,10 @@ class VsSpeakerParams(Structure):
                 ("proj_w", c_void_p), ("proj_b", c_void_p)]
 
 
+class VsResampleDims(Structure):
+    _fields_ = [(n, c_int) for n in ("sr_in", "sr_out", "L", "M", "H", "T", "tile_periods", "lds_bytes")] + [("bank_bytes", c_size_t)]
+
+
 class VsConvLayerGrad(Structure):
     _fields_ = [(n, c_void_p) for n in ("weight", "bias", "bn_weight", "bn_bias")]
 
@@ -226,6 +230,13 @@ SIGNATURES = {
     "vs_trim_workspace_bytes": (c_size_t, [c_longlong, c_int]),
     "vs_trim_bounds": (c_int, [_P, c_longlong, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "vs_mix_clips": (c_int, [_P, c_longlong, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    # sample-rate conversion
+    "vs_resample_plan": (c_int, [c_int, c_int, POINTER(VsResampleDims)]),
+    "vs_resample_out_len": (c_longlong, [POINTER(VsResampleDims), c_longlong]),
+    "vs_resample_bank": (c_int, [POINTER(VsResampleDims), _P, _P]),
+    "vs_resample": (c_int, [POINTER(VsResampleDims), _P, _P, c_longlong, c_longlong, c_longlong, c_longlong, _P, c_longlong, c_longlong,
+                            c_longlong, c_int, _P]),
+    "vs_resample_clips": (c_int, [POINTER(VsResampleDims), _P, _P, c_longlong, _P, c_longlong, _P, _P, c_int, _P]),
 }
 
 _lib = None

@@ -110,10 +110,41 @@ def griffin_lim(spec: torch.Tensor, audio_cfg, n_iter: int = None, power: float 
     return (wav, res) if return_residual else wav
 
 
-def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg, refine_iters: int = 0) -> torch.Tensor:
+_RESAMPLERS = {}
+
+
+def resampler(sr_in: int, sr_out: int, device):
+    """The ``resample.Resampler`` of this pair of rates on this device (its tap bank is built once and kept)."""
+    from .resample import Resampler
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(sr_in), int(sr_out), device)
+    if key not in _RESAMPLERS:
+        _RESAMPLERS[key] = Resampler(sr_in, sr_out, device)
+    return _RESAMPLERS[key]
+
+
+def resample(wav: torch.Tensor, sr_in: int, sr_out: int) -> torch.Tensor:
+    """wav [n] or [B, n] at ``sr_in`` -> [.., ceil(n sr_out / sr_in)] at ``sr_out`` (``librosa.load(path, sr=sr_out)``'s conversion,
+    csrc/resample.hip)."""
+    return resampler(sr_in, sr_out, wav.device)(wav)
+
+
+def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg, refine_iters: int = 0, sample_rate: int = None) -> torch.Tensor:
     """Target-speaker waveform for a batch of 3 s mixtures, all on the device:
     wav [B, hop*(T-1)], dvec [B, emb_dim] -> est_wav [B, hop*(T-1)]   (test.py's loop body).  refine_iters > 0: that many
-    Griffin-Lim rounds on the masked spectrogram, started from the mixture's phase (``griffin_lim`` with power 1)."""
+    Griffin-Lim rounds on the masked spectrogram, started from the mixture's phase (``griffin_lim`` with power 1).
+    sample_rate: the rate of ``wav`` when it is not ``audio_cfg["sample_rate"]`` (16000 when the config names none); wav is then
+    [B, n] for any n: converted to the configured rate, padded with zeros to a multiple of hop_length, separated, converted back
+    and cut to n samples."""
+    own = int(audio_cfg.get("sample_rate", 16000))
+    if sample_rate is not None and int(sample_rate) != own:
+        n, hop = wav.shape[1], int(audio_cfg["hop_length"])
+        x = resample(wav, int(sample_rate), own)
+        x = torch.nn.functional.pad(x, (0, -x.shape[1] % hop))
+        est = separate(model, x, dvec, audio_cfg, refine_iters)
+        return resample(est, own, int(sample_rate))[:, :n]
     spec, phase = wav_to_spec(wav, audio_cfg)
     with torch.no_grad():
         mask = model(spec, dvec)
@@ -256,6 +287,65 @@ class StreamingSeparator:
         self._spec, self._phase, self._mask = self._spec[:, s0 - self._s0:], self._phase[:, s0 - self._s0:], self._mask[:, s0 - self._s0:]
         self._s0 = s0
         return out
+
+
+class StreamingSeparatorAtRate:
+    """``StreamingSeparator`` for a stream at ``sample_rate`` instead of the configured rate (a sound card's 48000 or 44100):
+    ``push(samples [B, k])`` for any k returns the separated samples that became final ([B, m], m >= 0, at ``sample_rate``),
+    ``finish()`` the rest; the concatenation has exactly the pushed length.  A ``resample.StreamingResampler`` on each side; the
+    converted samples wait here until a multiple of hop_length is pending (at ``finish()`` the last block is padded with zeros).
+    What it returns is ``StreamingSeparator`` fed the whole converted stream (so padded), converted back and cut."""
+
+    def __init__(self, model, dvec: torch.Tensor, audio_cfg, C: int, R: int, sample_rate: int):
+        from .resample import StreamingResampler
+        own = int(audio_cfg.get("sample_rate", 16000))
+        self.sample_rate, self.own_rate = int(sample_rate), own
+        self.hop = int(audio_cfg["hop_length"])
+        self.sep = StreamingSeparator(model, dvec, audio_cfg, C, R)
+        self.down = StreamingResampler(self.sample_rate, own, dvec.device, resampler=resampler(self.sample_rate, own, dvec.device))
+        self.up = StreamingResampler(own, self.sample_rate, dvec.device, resampler=resampler(own, self.sample_rate, dvec.device))
+        self.finished = False
+        self._pending = None                     # converted samples not yet handed to the separator (fewer than hop after a push)
+        self._pushed = self._returned = 0        # at sample_rate
+
+    @property
+    def latency_samples(self) -> int:
+        """At ``sample_rate``: a sample is returned once this many more have been pushed.  Its converted sample exists H_down
+        pushed samples later; at the configured rate it then waits for its hop to fill (hop_length), for the separator
+        (``StreamingSeparator.latency_samples``) and for the H_up samples behind it that the conversion back reads."""
+        own = self.hop + self.sep.latency_samples + self.up.dims.H
+        return self.down.dims.H + -(-own * self.sample_rate // self.own_rate)
+
+    def _feed(self, x: torch.Tensor, last: bool) -> torch.Tensor:
+        self._pending = x if self._pending is None else torch.cat((self._pending, x), dim=1)
+        if last:
+            self._pending = torch.nn.functional.pad(self._pending, (0, -self._pending.shape[1] % self.hop))
+        n = self._pending.shape[1] // self.hop * self.hop
+        block, self._pending = self._pending[:, :n].contiguous(), self._pending[:, n:]
+        outs = [self.up.push(self.sep.push(block))] if n else []
+        if last:
+            outs += [self.up.push(self.sep.finish()), self.up.finish()]
+        if not outs:
+            return x.new_empty(x.shape[0], 0)
+        out = torch.cat(outs, dim=1)[:, :self._pushed - self._returned]
+        self._returned += out.shape[1]
+        return out
+
+    def push(self, samples: torch.Tensor) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("StreamingSeparatorAtRate: the stream has been finished")
+        if samples.dim() != 2:
+            raise ValueError(f"samples must be [B, k], got {tuple(samples.shape)}")
+        self._pushed += samples.shape[1]
+        return self._feed(self.down.push(samples.contiguous()), False)
+
+    def finish(self) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("StreamingSeparatorAtRate: the stream has been finished")
+        if self._pushed == 0:
+            raise RuntimeError("StreamingSeparatorAtRate: finish() on a stream that never received a sample")
+        self.finished = True
+        return self._feed(self.down.finish(), True)
 
 
 # frames a ragged batch may occupy (items * longest item): 64 clips of 3 s, the batch the workspace of the 3 s path is sized for anyway

@@ -63,9 +63,52 @@ class ClipPool:
         self._trim()
 
     @classmethod
-    def from_files(cls, paths: Sequence[str], sample_rate: int, device="cuda:0") -> "ClipPool":
-        from .trainer import load_wav
-        return cls([load_wav(p, sample_rate) for p in paths], device)
+    def from_files(cls, paths: Sequence[str], sample_rate: int, device="cuda:0", resample: bool = False) -> "ClipPool":
+        """resample=False: every file must be at ``sample_rate`` (``load_wav`` raises otherwise).  resample=True: what
+        ``librosa.load(path, sr=sample_rate)`` does -- the files are grouped by their own rate, every off-rate group is uploaded as it
+        is and converted by one ``vs_resample_clips`` call straight into the pool's flat buffer, files at ``sample_rate`` are copied."""
+        from .trainer import load_wav, load_wav_native
+        if not resample:
+            return cls([load_wav(p, sample_rate) for p in paths], device)
+        from .resample import Resampler, out_len, plan
+        loaded = [load_wav_native(p) for p in paths]
+        plans = {sr: plan(sr, sample_rate) for sr in sorted({sr for _, sr in loaded})}
+        # the pool's clips are the converted ones: lay them out first (ClipPool checks their sizes), then fill them group by group
+        sizes = [out_len(plans[sr], w.numel()) for w, sr in loaded]
+        self = cls.__new__(cls)
+        self._layout(sizes, device)
+        for sr in plans:
+            group = [k for k, (_, r) in enumerate(loaded) if r == sr]
+            if sr == sample_rate:
+                for k in group:
+                    o = int(self.offsets[k])
+                    self.flat[o:o + sizes[k]].copy_(loaded[k][0])
+                continue
+            n_in = torch.tensor([loaded[k][0].numel() for k in group], dtype=torch.int64)
+            table = torch.stack((n_in.cumsum(0) - n_in, n_in, self.offsets[group]), dim=1)
+            staged = torch.empty(int(n_in.sum()), dtype=torch.float32, device=self.device)
+            for o, k in zip(table[:, 0].tolist(), group):
+                staged[o:o + loaded[k][0].numel()].copy_(loaded[k][0])
+            Resampler(sr, sample_rate, self.device).clips_into(staged, self.flat, table)
+        self._trim()
+        return self
+
+    def _layout(self, sizes: Sequence[int], device) -> None:
+        """offsets / total / an uninitialised ``flat`` for clips of ``sizes`` samples."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.VoiceSplitHipError(f"ClipPool on {device}: this path only runs on an MI355X (HIP) device; there is no CPU fallback")
+        if len(sizes) == 0:
+            raise ValueError("ClipPool: no clips")
+        for k, n in enumerate(sizes):
+            if n < MIN_CLIP:
+                raise ValueError(f"clip {k} has {n} samples, fewer than {MIN_CLIP}: silence trimming is not defined for it")
+        self.device = device
+        self.offsets = torch.zeros(len(sizes) + 1, dtype=torch.int64)
+        self.offsets[1:] = torch.tensor(list(sizes), dtype=torch.int64).cumsum(0)
+        self.total = int(self.offsets[-1])
+        self.flat = torch.empty(self.total, dtype=torch.float32, device=device)
+        self.offsets_dev = self.offsets.to(device)
 
     @classmethod
     def planned(cls, lengths: Sequence[int], bounds: Sequence[Sequence[int]], peak: Optional[Sequence[float]] = None) -> "ClipPool":
@@ -389,6 +432,8 @@ def main(argv=None):
     ap.add_argument("--speaker-checkpoint", default=None, help="embedder.pt: also write *-emb.pt with the GE2E speaker encoder")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--resample", action="store_true", help="convert files at another rate to the configured one on the device "
+                    "(librosa.load(path, sr=sample_rate)); without it such a file is an error")
     args = ap.parse_args(argv)
     c = load_config(args.config)
     audio_cfg = c.audio[c.audio["backend"]]
@@ -407,7 +452,7 @@ def main(argv=None):
         paths, triplets, numbers, skipped = read_triplet_csv(path, args.dataset_root_dir, bool(args.librispeech))
         written = 0
         if triplets:
-            pool = ClipPool.from_files(paths, int(audio_cfg["sample_rate"]), args.device)
+            pool = ClipPool.from_files(paths, int(audio_cfg["sample_rate"]), args.device, resample=args.resample)
             written = write_dataset(pool, triplets, numbers, out, audio_cfg, c.audio["audio_len"], form, args.batch, encoder)
         print(f"{name}: {written} triplets written to {out}, {len(triplets) - written} too short or silent, "
               f"{skipped} skipped for a missing file")

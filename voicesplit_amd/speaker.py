@@ -291,6 +291,23 @@ def embed_directory(encoder, data_dir: str, audio_cfg, batch: int = 64, device="
     return good
 
 
+def resampling_loader(device="cuda:0"):
+    """A ``load_wav(path, sample_rate)`` for ``embed_directory`` that accepts a file at any rate and converts it on the device
+    (``librosa.load(path, sr=sample_rate)``); one ``resample.Resampler`` per source rate."""
+    from .resample import Resampler
+    from .trainer import load_wav_native
+    resamplers = {}
+
+    def load(path, sample_rate):
+        wav, native = load_wav_native(path)
+        if native == sample_rate:
+            return wav
+        if native not in resamplers:
+            resamplers[native] = Resampler(native, sample_rate, device)
+        return resamplers[native](wav.to(device))
+    return load
+
+
 def main(argv=None):
     from .config import default_config, load_config
     ap = argparse.ArgumentParser(description="Write the *-emb.pt speaker embeddings of a data directory")
@@ -300,6 +317,7 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--root", default="..", help="directory the paths inside *-ref_emb.wav are relative to")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--resample", action="store_true", help="convert reference clips at another rate to the configured one on the device")
     args = ap.parse_args(argv)
     c = load_config(args.config) if args.config else default_config()
     audio_cfg = c.audio[c.audio["backend"]]
@@ -307,7 +325,8 @@ def main(argv=None):
     enc.load_state_dict(torch.load(args.checkpoint, map_location="cpu"), strict=True)
     enc = enc.eval().to(args.device)
     for d in args.data_dir:
-        n = embed_directory(enc, d, audio_cfg, batch=args.batch, device=args.device, root=args.root)
+        n = embed_directory(enc, d, audio_cfg, batch=args.batch, device=args.device, root=args.root,
+                            load_wav=resampling_loader(args.device) if args.resample else None)
         print(f"{d}: {n} embeddings written")
 
 

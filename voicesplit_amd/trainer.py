@@ -555,6 +555,14 @@ def load_wav(path: str, sample_rate: int) -> torch.Tensor:
     return t.mean(dim=1) if t.dim() == 2 else t
 
 
+def load_wav_native(path: str):
+    """(wav, sample_rate): ``load_wav``'s decoding at whatever rate the file has, for callers that resample on the device
+    (``resample.Resampler``, ``ClipPool.from_files(resample=True)``)."""
+    from scipy.io import wavfile
+    sr, _ = wavfile.read(path, mmap=True)
+    return load_wav(path, int(sr)), int(sr)
+
+
 class SpecWavDataset:
     """The training items of utils/dataset.py:8-41 read from ``c.dataset['train_dir']`` with the
     globs of ``c.dataset['format']``: emb ``*-emb.pt``, target spectrogram ``*-target.pt``, and the
@@ -708,7 +716,7 @@ def _mixture_batches(args, c, acfg, b, rank, world, dev):
     paths, triplets, numbers, skipped = mixing.read_triplet_csv(args.mix_csv, args.mix_root, args.librispeech)
     if not triplets:
         raise ValueError(f"{args.mix_csv}: no triplet with all three files under {args.mix_root}")
-    pool = mixing.ClipPool.from_files(paths, int(acfg["sample_rate"]), dev)
+    pool = mixing.ClipPool.from_files(paths, int(acfg["sample_rate"]), dev, resample=bool(getattr(args, "resample", False)))
     L = mixing.samples_for(acfg, c.audio["audio_len"])
     if args.emb_dir:
         embs = [torch.load(os.path.join(args.emb_dir, "%06d-emb.pt" % n)) for n in numbers]
@@ -752,6 +760,7 @@ def main(argv=None):
                     "the mixtures are made on the GPU (voicesplit_amd.mixing) instead of read from c.dataset")
     ap.add_argument("--mix-root", default=".", help="directory the CSV's names are relative to")
     ap.add_argument("--librispeech", action="store_true", help="the CSV holds LibriSpeech utterance ids (preprocess_by_csv.py -l)")
+    ap.add_argument("--resample", action="store_true", help="--mix-csv: convert files at another rate to the configured one on the device")
     ap.add_argument("--mix-crop", choices=("head", "random"), default="head", help="head: the reference's [:audio_len]; random: a fresh crop every epoch")
     ap.add_argument("--emb-dir", default=None, help="precomputed %%06d-emb.pt per CSV row, instead of embedding the reference clips here")
     ap.add_argument("--speaker-checkpoint", default=None, help="embedder.pt of the GE2E speaker encoder (--mix-csv without --emb-dir)")
