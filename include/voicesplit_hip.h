@@ -830,6 +830,75 @@ int vs_mix_clips(const float* samples, long long total, const long long* clean_a
                  float* mixed_wav, float* target_wav, float* norm, int* valid, int* invalid_count, void* stream);
 
 /* =============================================================================================
+ * ABI 11 (additive entries).  The noisy training items WITHOUT voice overlay: the arithmetic of mix_wavfiles_without_voice_overlay
+ * (utils/generic_utils.py:27-296).  The target speaker and the interferer take turns, two noise recordings run under the whole item,
+ * and every triplet yields four items.  librosa.effects.split is RESTATED here as vs_trim_bounds restates trim: NOBODY HAS COMPARED
+ * IT WITH A LIBROSA RUN.  This text is the contract for the C entries; tests/overlay_ref.py restates the whole recipe in fp64.
+ *
+ * vs_clip_range: range[i] = (min, max) of samples[offsets[i] + bounds[i][0] : offsets[i] + bounds[i][1]] in fp32, exact: what
+ * sklearn.preprocessing.minmax_scale reads of a trimmed clip.  bounds [N][2] int32 on the device (vs_trim_bounds' output; clamped
+ * to the clip), or NULL: the whole clip.  An empty region gives (0, 0).  offsets / offsets_host as for vs_trim_bounds (a clip may
+ * have any length from 0 to 2^30 here).  One launch, a workgroup per clip; once per pool.
+ * ============================================================================================= */
+int vs_clip_range(const float* samples, long long total, const long long* offsets_host, const long long* offsets, const int* bounds,
+                  int N, float* range, void* stream);
+/* vs_split_point: librosa.effects.split(y, top_db) at its defaults (frame_length 2048, hop_length 512, ref = np.max) for B regions
+ * y_b = samples[at_b : at_b + n_b] of the flat buffer (any alignment), with mse[f] and the clamp of vs_trim_bounds:
+ *   frame f (0 .. n / 512) is non-silent when max(1e-10, mse[f]) / max(1e-10, max_f mse[f]) > ratio[b]
+ *   an interval is a maximal run [f0, f1) of non-silent frames; in samples [512 f0, min(n, 512 f1))
+ *   count[b] = number of intervals (>= 1: the loudest frame is never silent; an all-zero region is one interval (0, n))
+ *   split[b] = end of interval number count / 2 (from 0): the reference's clip_idx = parts[int(len(parts) / 2)][1]
+ * ratio [B] fp64 on the device: 10^(-top_db / 10), 1e-2 for the clean voice (top_db = 20), 10^-1.5 for the interferer (15).
+ * The promises above hold for 0 < ratio < 1; the ratios live on the device and are not checked: with ratio >= 1 (or NaN) no
+ * frame is non-silent, and count[b] = 0, split[b] = n, no interval is written.
+ * regions [B][2] int64 on the device = (at, n); regions_host the same values in HOST memory, checked here before anything is
+ * launched: 1025 <= n <= 2^30 and 0 <= at <= total - n, else -1 and a message.  The reflect padding reflects at the region's own
+ * ends: no sample outside [at, at + n) is read.  intervals, when not NULL: [B][cap][2] int32, the first min(count, cap) intervals of
+ * every region (the rest of a row is not written).  workspace: vs_split_workspace_bytes(n_max, B) bytes, 256-byte aligned, n_max >=
+ * every n.  Sums in fp64.  1 <= B <= 2^24.  One launch, a workgroup per region. */
+size_t vs_split_workspace_bytes(long long n_max, int B);
+int vs_split_point(const float* samples, long long total, const long long* regions_host, const long long* regions,
+                   const double* ratio, int B, int* count, int* split, int* intervals, int cap, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* vs_mix_sequence: one batch of items, each up to three segments end to end over one continuous noise bed.
+ * Segment s of item b is samples[src_at[s] : src_at[s] + len[s]] (len 0: absent; the item's length n = len[0] + len[1] + len[2] <= L).
+ * noise1_at / noise2_at: the index in `noise` (a second flat buffer, noise_total samples) that goes with OUTPUT sample 0 -- the
+ * noise index always runs on with the output index ("noise without interruption", :134-137).  With s the segment of output sample
+ * t, x its sample, and n1 = noise[noise1_at + t], n2 = noise[noise2_at + t], all fp32 and in this order:
+ *   v = fmaf(gain[s], x, bias[s])
+ *   if noise_sel[s] >= 0:  v = v + fmaf(ngain[noise_sel[s]], n1 + n2, nbias[noise_sel[s]])
+ *   mixed[t] = v / norm,   target[t] = in_target[s] ? v / norm : 0.0f          (IEEE fp32 division)
+ * ngain / nbias are formed on the device, nothing is read back: with (nmin, nmax) the fp32 minimum and maximum of
+ * noise[range_at1 + j] + noise[range_at2 + j] (fp32 sum), j < range_len, and den = double(nmax) - double(nmin), or 1 when that is 0,
+ *   scale_k = (double(hi[k]) - double(lo[k])) / den,  ngain[k] = float(scale_k),  nbias[k] = float(double(lo[k]) - double(nmin) * scale_k)
+ * (fp64, no fused multiply-add): minmax_scale(noise, feature_range=(lo[k], hi[k])) for k = 0, the plain noise draw (:105-110),
+ * and k = 1, the random-amplitude draw (:45-49).
+ *   m = max_t |v|,  norm[b] = float(1.1 * double(m));  with norm_in ([B], device) the maximum is skipped and norm[b] = norm_in[b]
+ * (kinds 2 and 3 divide by kind 1's norm_factor, :218-227).  Samples n .. L - 1 of both rows are 0.0f.
+ * valid[b]: 1; 0 when norm[b] == 0 (rows of zeros); -1 and rows of zeros, with nothing of the item read, when a len is negative or
+ * n > L, a segment leaves `samples`, noise_sel is outside -1 .. 1, or -- for an item with a noise_sel >= 0 -- [noise*_at, + n) or
+ * [range_at*, + range_len) leaves `noise` or range_len is outside 1 .. R.  invalid_count as for vs_mix_clips.
+ * aux [B][8] fp32: {nmin, nmax, m, ngain[0], nbias[0], ngain[1], nbias[1], 0} (zeros for an item without noise; m is 0 with
+ * norm_in); it doubles as the call's scratch.  mixed_wav, target_wav [B][L], 16-byte aligned; BOTH NULL: only norm, aux and valid
+ * are computed (the planner gets every triplet's kind-1 norm this way).  L, R: row capacity and the largest range_len, 1 .. 2^30.
+ * 1 <= B <= 65535.  Minimum and maxima are order-independent: two calls give the same bits.  Passes on `stream`: clear (a memset),
+ * noise range, maximum, scale, finalise; nothing is allocated, no environment variable is read. */
+typedef struct vs_seq_item {
+  long long src_at[3];              /* index in `samples` of each segment's first sample */
+  long long noise1_at, noise2_at;   /* index in `noise` for output sample 0 */
+  long long range_at1, range_at2;   /* the slice whose n1 + n2 minimum and maximum feed the noise affines */
+  int len[3];
+  int in_target[3];
+  int noise_sel[3];                 /* -1: no noise, 0: the plain affine, 1: the random-amplitude affine */
+  int range_len;
+  float gain[3], bias[3];
+  float lo[2], hi[2];               /* feature ranges: [0] plain, [1] random amplitude */
+} vs_seq_item;                      /* 136 bytes: 7 int64, 10 int32, 10 fp32 */
+int vs_mix_sequence(const float* samples, long long total, const float* noise, long long noise_total, const vs_seq_item* items,
+                    int B, int L, int R, const float* norm_in, float* mixed_wav, float* target_wav, float* norm, float* aux,
+                    int* valid, int* invalid_count, void* stream);
+
+/* =============================================================================================
  * ABI 11 (additive entries).  Sample-rate conversion on the device: what librosa.load(path, sr=...) does on the CPU in front of
  * mix_wavfiles and of both audio processors' load_wav.  The filter is a Kaiser-windowed sinc with the constants of resampy's
  * kaiser_best AS REMEMBERED, its window evaluated analytically and not through resampy's interpolated table: RESTATED, NOT

@@ -230,6 +230,10 @@ SIGNATURES = {
     "vs_trim_workspace_bytes": (c_size_t, [c_longlong, c_int]),
     "vs_trim_bounds": (c_int, [_P, c_longlong, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "vs_mix_clips": (c_int, [_P, c_longlong, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "vs_clip_range": (c_int, [_P, c_longlong, _P, _P, _P, c_int, _P, _P]),
+    "vs_split_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "vs_split_point": (c_int, [_P, c_longlong, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "vs_mix_sequence": (c_int, [_P, c_longlong, _P, c_longlong, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     # sample-rate conversion
     "vs_resample_plan": (c_int, [c_int, c_int, POINTER(VsResampleDims)]),
     "vs_resample_out_len": (c_longlong, [POINTER(VsResampleDims), c_longlong]),

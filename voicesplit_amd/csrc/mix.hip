@@ -7,7 +7,7 @@
 // vs_trim_bounds: librosa.effects.trim(y, top_db=20) with its defaults (frame_length 2048, hop_length 512, ref=np.max), as
 // stated in include/voicesplit_hip.h.  A frame is four consecutive 512-sample blocks of the reflect-padded clip, so
 //   trim_clip_kernel  one workgroup per clip, three phases behind workgroup barriers:
-//     1. a wave per 512-sample block: its sum of squares in fp64 (fp32 squares are exact in fp64) -> the clip's slice of the
+//     1. a wave per 512-sample block (block_sumsq, mix_common.h): its sum of squares in fp64 (fp32 squares are exact in fp64) -> the clip's slice of the
 //        workspace.  A block that lies inside the clip is read with 16-byte loads from the first 16-byte boundary on, the up to
 //        three samples in front and behind by single lanes (clip offsets are arbitrary); the blocks that touch the reflect padding
 //        (the first two and the last three or four of a clip) index sample by sample and never leave [0, n) of their own clip;
@@ -31,23 +31,15 @@
 
 #include "../../include/voicesplit_hip.h"
 #include "vs_internal.h"
+#include "mix_common.h"
 
 namespace {
 
-constexpr int kFrame = 2048, kHop = 512, kPad = kFrame / 2;
-constexpr int kMinClip = kPad + 1;                     // the reflection needs y[1024]
-constexpr long long kMaxClip = 1LL << 30;              // bounds are int32
 constexpr int kMaxClips = 1 << 24;
-constexpr double kAmin = 1e-10, kRatio = 1e-2;         // power_to_db(amin=1e-10), top_db = 20
+constexpr double kRatio = 1e-2;                        // top_db = 20
 
 // clip i owns ws[floor(offsets[i] / 512) + 4 i, + n_i / 512 + 4): disjoint for consecutive clips, no prefix sum needed
 __host__ __device__ inline long long trim_slice(long long off, long long i) { return off / kHop + 4 * i; }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 __global__ void __launch_bounds__(256) trim_clip_kernel(const float* __restrict__ samples, const long long* __restrict__ offsets,
                                                         double* __restrict__ ws, int* __restrict__ bounds, float* __restrict__ peak) {
@@ -63,35 +55,7 @@ __global__ void __launch_bounds__(256) trim_clip_kernel(const float* __restrict_
 
   // 1. block b = padded samples [512 b, 512 b + 512) = clip samples k0 .. k0 + 511, k0 = 512 b - 1024
   for (int b = wave; b < nblocks; b += 4) {
-    const int k0 = b * kHop - kPad;
-    double acc = 0.0;
-    if (k0 >= 0 && k0 + kHop <= n) {
-      const long long g0 = off + k0;                                   // index in the flat buffer (its base is 16-byte aligned)
-      const int head = (int)((4 - (g0 & 3)) & 3);                      // samples in front of the first 16-byte boundary
-      const int nvec = (kHop - head) >> 2, tail = (kHop - head) & 3;
-      const float4* __restrict__ v = reinterpret_cast<const float4*>(samples + g0 + head);
-      for (int q = lane; q < nvec; q += 64) {
-        const float4 x = v[q];
-        acc += (double)x.x * x.x + (double)x.y * x.y + (double)x.z * x.z + (double)x.w * x.w;
-      }
-      if (lane < head) {
-        const float x = y[k0 + lane];
-        acc += (double)x * x;
-      }
-      if (lane < tail) {
-        const float x = y[k0 + kHop - tail + lane];
-        acc += (double)x * x;
-      }
-    } else {
-      for (int j = lane; j < kHop; j += 64) {
-        int k = k0 + j;
-        if (k < 0) k = -k;                                             // yp[1024 - k] = y[k]
-        if (k >= n) k = 2 * (n - 1) - k;                               // yp[1024 + n - 1 + k] = y[n - 1 - k]
-        const float x = y[k];                                          // 0 <= k < n for n >= 1025
-        acc += (double)x * x;
-      }
-    }
-    acc = wave_sum_f64(acc);
+    const double acc = block_sumsq(samples, off, n, b, lane);
     if (lane == 0) s[b] = acc;
   }
   __syncthreads();                                                     // the block sums of this clip, written by this workgroup
@@ -149,7 +113,6 @@ __global__ void __launch_bounds__(256) trim_clip_kernel(const float* __restrict_
 
 // ---- mixtures ---------------------------------------------------------------------------------------------------------------
 constexpr int kMixChunk = 2048;                        // samples of one row per workgroup: 256 lanes x 2 x 4
-typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // four floats at any sample index
 
 __device__ __forceinline__ bool mix_in_range(long long at, int L, long long total) { return at >= 0 && at <= total - L; }
 
@@ -183,8 +146,6 @@ __global__ void __launch_bounds__(256) mix_max_kernel(const float* __restrict__ 
     if (m > 0.f) atomicMax(slot + b, __float_as_uint(m));              // m >= 0: the order of the bit patterns is the order of the values
   }
 }
-
-__device__ __forceinline__ float mix_norm(float m) { return (float)(1.1 * (double)m); }
 
 __global__ void __launch_bounds__(256) mix_scale_kernel(const float* __restrict__ samples, long long total,
                                                         const long long* __restrict__ clean_at, const long long* __restrict__ interf_at,

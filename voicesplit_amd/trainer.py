@@ -717,6 +717,8 @@ def _mixture_batches(args, c, acfg, b, rank, world, dev):
     if not triplets:
         raise ValueError(f"{args.mix_csv}: no triplet with all three files under {args.mix_root}")
     pool = mixing.ClipPool.from_files(paths, int(acfg["sample_rate"]), dev, resample=bool(getattr(args, "resample", False)))
+    if getattr(args, "no_overlay", False):
+        return _overlay_batches(args, c, acfg, b, rank, world, dev, pool, triplets, numbers)
     L = mixing.samples_for(acfg, c.audio["audio_len"])
     if args.emb_dir:
         embs = [torch.load(os.path.join(args.emb_dir, "%06d-emb.pt" % n)) for n in numbers]
@@ -745,6 +747,45 @@ def _mixture_batches(args, c, acfg, b, rank, world, dev):
                                  seed=c.train_config["seed"], emb_rows=rows)
 
 
+def _overlay_batches(args, c, acfg, b, rank, world, dev, pool, triplets, numbers):
+    """``--mix-csv ... --noise-csv FILE --no-overlay``: a second resident pool of noise recordings and a ``mixing.OverlayBatches``
+    (the speakers take turns over the noise; four items per triplet, packed by length).  Every rank plans the whole epoch alike and
+    takes its share of every global batch, so all ranks run the same number of steps (``OverlayBatches``)."""
+    from . import mixing
+    noise_pool = mixing.ClipPool.from_files(mixing.read_noise_csv(args.noise_csv, args.mix_root), int(acfg["sample_rate"]), dev,
+                                            resample=bool(getattr(args, "resample", False)), trim=False)
+    if args.emb_dir:
+        table = None
+        for (_, ref, _), n in zip(triplets, numbers):                           # one embedding per reference clip: its first row's
+            e = torch.load(os.path.join(args.emb_dir, "%06d-emb.pt" % n))
+            if e.tolist() == [0]:
+                continue
+            if table is None:
+                table = torch.zeros(len(pool), e.numel())
+            if not table[ref].any():
+                table[ref] = e.float().reshape(-1)
+        if table is None:
+            raise ValueError(f"{args.emb_dir}: no embedding for any row of {args.mix_csv}")
+        table = table.to(dev)
+    else:
+        if not args.speaker_checkpoint:
+            raise ValueError("--mix-csv needs --emb-dir or --speaker-checkpoint")
+        from .speaker import SpeakerEncoder
+        enc = SpeakerEncoder(num_mels=int(acfg.get("num_mels", 40)))
+        enc.load_state_dict(torch.load(args.speaker_checkpoint, map_location="cpu"), strict=True)
+        refs = sorted({t[1] for t in triplets})
+        table = torch.zeros(len(pool), enc.emb_dim, device=dev)
+        table[torch.tensor(refs, device=dev)] = pool.embed(enc.eval().to(dev), acfg, refs)
+    has = (table.abs().sum(dim=1) > 0).tolist()                                 # utils/dataset.py:93-95
+    kept = [t for t in triplets if has[t[1]]]
+    if rank == 0:
+        print(f"{len(kept)} triplets from {len(pool)} clips and {len(noise_pool)} noise recordings "
+              f"({(pool.total + noise_pool.total) / acfg['sample_rate'] / 3600:.2f} h on the device), without voice overlay; "
+              f"{len(triplets) - len(kept)} without an embedding; the planner drops short and silent ones per epoch", flush=True)
+    shard = EpochShard(len(kept), b, rank, world, c.train_config["seed"])
+    return mixing.OverlayBatches(pool, noise_pool, kept, table, acfg, shard, seed=c.train_config["seed"])
+
+
 def main(argv=None):
     """``python -m torch.distributed.run --nproc-per-node N -m voicesplit_amd.trainer -c config.json``
     (train.py's CLI: --config_path/-c, --checkpoint_path; plus --synthetic-steps for a dry run)."""
@@ -762,9 +803,14 @@ def main(argv=None):
     ap.add_argument("--librispeech", action="store_true", help="the CSV holds LibriSpeech utterance ids (preprocess_by_csv.py -l)")
     ap.add_argument("--resample", action="store_true", help="--mix-csv: convert files at another rate to the configured one on the device")
     ap.add_argument("--mix-crop", choices=("head", "random"), default="head", help="head: the reference's [:audio_len]; random: a fresh crop every epoch")
+    ap.add_argument("--no-overlay", action="store_true", help="--mix-csv with --noise-csv: the speakers take turns over two noise "
+                    "recordings, four items per triplet (preprocess_by_csv_without_voice_overlay.py)")
+    ap.add_argument("--noise-csv", default=None, help="--no-overlay: one noise file per line, relative to --mix-root")
     ap.add_argument("--emb-dir", default=None, help="precomputed %%06d-emb.pt per CSV row, instead of embedding the reference clips here")
     ap.add_argument("--speaker-checkpoint", default=None, help="embedder.pt of the GE2E speaker encoder (--mix-csv without --emb-dir)")
     args = ap.parse_args(argv)
+    if args.no_overlay != bool(args.noise_csv) or (args.no_overlay and not args.mix_csv):
+        ap.error("--no-overlay, --noise-csv and --mix-csv go together")
     c = load_config(args.config_path)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
