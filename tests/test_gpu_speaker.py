@@ -207,6 +207,22 @@ def test_logmel_against_fp64_restatement():
             assert e_gpu <= 4.0 * e_32
 
 
+@pytest.mark.parametrize("n", [601, 800, 1237])
+def test_logmel_short_clips_against_fp64_restatement(n):
+    """The shortest legal clip (n_fft / 2 + 1 samples: both reflections reach across the whole clip), a multiple of the hop and a
+    non-multiple, cut from demo clip 0 at sample 16000 (largest mel power of the three slices 6.5 .. 9.4: speech, not a pause).
+    The linear criterion of test_logmel_against_fp64_restatement, same bound."""
+    from voicesplit_amd import logmel, mel_filterbank
+    w = demo_wavs()[0][16000:16000 + n].contiguous()
+    got = logmel(w.to(DEV), AUDIO).double().cpu()
+    P_ref = mel_filterbank(16000, 1200, 40) @ _stft_power(w, torch.float64)
+    assert got.shape == P_ref.shape == (40, 1 + n // 160)
+    assert P_ref.max().item() > 1e-3
+    lin = ((10.0 ** got - 1e-6) - P_ref).abs().max().item() / P_ref.max().item()
+    print(f"logmel n={n}: linear {lin:.2e}")
+    assert lin <= BOUND
+
+
 def test_separate_with_reference_equals_separate_with_the_embedding():
     import voicesplit_amd as V
     from voicesplit_amd import audio

@@ -5,8 +5,8 @@
 //   x    = nn.LSTM(n_mels -> H, layers)(mel.unfold(1, window, stride))[:, -1, :]                               [N][H]
 //   p    = Linear(H -> E)(x);  dvec = mean over the utterance's windows of p / |p|_2
 //
-// Front end: the STFT is vs_wav_to_spec's (frames, split-f16 GEMM against the windowed DFT basis), with reflection at the clip's TRUE
-// end (any n > n_fft / 2), a power epilogue, the F -> n_mels contraction and the log.
+// Front end: the STFT is stft.hip's, the kernels vs_wav_to_spec launches (frames, split-f16 GEMM against the windowed DFT basis), on a
+// shape of one clip with reflection at the clip's TRUE end (any n > n_fft / 2); then a power epilogue, the F -> n_mels contraction and the log.
 //
 // Recurrence (the hot path): the batch is the number of windows N (6 for a 3 s clip, ~1000 for a preprocessing batch), H = 768,
 // three stacked layers, 80 steps.  Schedule: a WAVEFRONT of window + layers - 1 ticks; at tick d layer l runs its step t = d - l
@@ -23,7 +23,7 @@
 #include <math.h>
 
 #include "../../include/voicesplit_hip.h"
-#include "vs_internal.h"
+#include "stft_common.h"
 
 namespace {
 
@@ -150,11 +150,6 @@ void spk_pack_f32_kernel(const float* __restrict__ w_ih, const float* __restrict
     const int row = (int)(i / Kl), k = (int)(i - (long long)row * Kl);
     out[i] = spk_w_at(w_ih, w_hh, H, H, row, k);
   }
-}
-
-inline unsigned grid_for(long long n, unsigned cap = 2048) {
-  const long long nb = (n + 255) / 256;
-  return (unsigned)(nb < 1 ? 1 : (nb < (long long)cap ? nb : (long long)cap));
 }
 
 // ---- workspace of vs_speaker_embed --------------------------------------------------------------------------------------------
@@ -365,10 +360,10 @@ void spk_pool_kernel(const float* __restrict__ proj, const int* __restrict__ utt
 }
 
 // ---- log-mel front end --------------------------------------------------------------------------------------------------------
-struct MelShape { int n, T, F, n_fft, hop, win, lead, K, ldk, n_mels; };
 struct MelLayout { size_t frames, basis, reim, amax, scales, total; };
 
-int mel_shape(const vs_loss_dims* d, long long n, int n_mels, MelShape* s) {
+// stft_common.h's shape for ONE clip of n samples: T = 1 + n / hop frames, reflection at the clip's true end (S = n), librosa's window
+int mel_shape(const vs_loss_dims* d, long long n, int n_mels, VsStftShape* s) {
   VS_REQUIRE(d != nullptr, "wav_to_logmel: dims is NULL");
   VS_REQUIRE(d->F > 1 && d->hop > 0 && d->win > 0, "wav_to_logmel: bad dims F=%d hop=%d win=%d", d->F, d->hop, d->win);
   VS_REQUIRE(d->n_fft == 2 * (d->F - 1), "wav_to_logmel: num_freq F=%d must be n_fft/2+1 (n_fft=%d)", d->F, d->n_fft);
@@ -377,62 +372,27 @@ int mel_shape(const vs_loss_dims* d, long long n, int n_mels, MelShape* s) {
   VS_REQUIRE(n_mels >= 1 && n_mels <= 4096, "wav_to_logmel: n_mels=%d (1 .. 4096)", n_mels);
   VS_REQUIRE(n > d->n_fft / 2, "wav_to_logmel: clip of n=%lld samples is not longer than the reflect padding n_fft/2=%d", n, d->n_fft / 2);
   VS_REQUIRE(n <= (1LL << 28), "wav_to_logmel: n=%lld too large (one call per utterance)", n);
-  s->n = (int)n; s->F = d->F; s->n_fft = d->n_fft; s->hop = d->hop; s->win = d->win; s->n_mels = n_mels;
-  s->T = 1 + (int)(n / d->hop);
-  s->lead = d->n_fft / 2 - (d->n_fft - d->win) / 2;
-  s->K = 2 * d->F;
-  s->ldk = (s->K + 3) & ~3;
+  vs_stft_fill_shape(d, 1, 1 + (int)(n / d->hop), (int)n, s);
+  s->periodic = 1;
   return 0;
 }
 
-void mel_layout(const MelShape& s, MelLayout* L) {
+MelLayout mel_layout(const VsStftShape& s) {
+  MelLayout L;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-  L->frames = take((size_t)s.T * s.win * 4);
-  L->basis = take((size_t)s.K * s.win * 4);
-  L->reim = take((size_t)s.T * s.ldk * 4);
-  L->amax = take((size_t)VS_AMAX_SLOTS * 4);
-  L->scales = take(8 * 4);
-  L->total = off;
-}
-
-// frames[t][j] = hann[j] * wav_reflect[hop t - lead + j] (librosa.stft, center=True, reflect; periodic Hann of `win` centred in n_fft);
-// the clip ends where it ends: reflection about sample n - 1, n any length above n_fft / 2
-__global__ __launch_bounds__(256)
-void mel_frames_kernel(const float* __restrict__ wav, float* __restrict__ frames, MelShape s, unsigned* __restrict__ amax) {
-  const long long total = (long long)s.T * s.win;
-  float mx = 0.f;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int t = (int)(i / s.win), j = (int)(i - (long long)t * s.win);
-    int idx = s.hop * t - s.lead + j;
-    if (idx < 0) idx = -idx;
-    if (idx >= s.n) idx = 2 * (s.n - 1) - idx;
-    idx = idx < 0 ? 0 : (idx >= s.n ? s.n - 1 : idx);          // (n > n_fft / 2 makes one reflection enough; never read outside the clip)
-    const float w = 0.5f - 0.5f * cospif(2.0f * (float)j / (float)s.win);
-    const float v = w * wav[idx];
-    frames[i] = v;
-    mx = fmaxf(mx, fabsf(v));
-  }
-  vs_absmax_commit(mx, amax);
-}
-
-// basis[k][j]: Re_k = sum_j x_j cos(2 pi k n_j / N), Im_k = -sum_j x_j sin(...), n_j = (N - win) / 2 + j (exact angle reduction)
-__global__ void mel_basis_kernel(float* __restrict__ basis, MelShape s, float* __restrict__ scale2) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx == 0) { scale2[0] = 512.f; scale2[1] = 1.f / 512.f; }
-  if (idx >= s.K * s.win) return;
-  const int k = idx / s.win, j = idx - k * s.win;
-  const int kk = k < s.F ? k : k - s.F;
-  const int n = (s.n_fft - s.win) / 2 + j;
-  const int r = (int)(((long long)kk * n) % s.n_fft);
-  float sn, cs;
-  sincospif(2.0f * (float)r / (float)s.n_fft, &sn, &cs);
-  basis[idx] = k < s.F ? cs : -sn;
+  L.frames = take((size_t)s.T * s.win * 4);
+  L.basis = take((size_t)s.K * s.win * 4);
+  L.reim = take((size_t)s.T * s.ldk * 4);
+  L.amax = take((size_t)VS_AMAX_SLOTS * 4);
+  L.scales = take(8 * 4);
+  L.total = off;
+  return L;
 }
 
 // mel[m][t] = log10(sum_f mel_basis[m][f] (re^2 + im^2) + 1e-6): one workgroup per frame, the power row in LDS, one wave per mel row
 __global__ __launch_bounds__(256)
-void mel_power_log_kernel(const float* __restrict__ reim, const float* __restrict__ mel_basis, float* __restrict__ mel, MelShape s) {
+void mel_power_log_kernel(const float* __restrict__ reim, const float* __restrict__ mel_basis, float* __restrict__ mel, VsStftShape s, int n_mels) {
   extern __shared__ float pw[];
   const int t = blockIdx.x;
   const float* __restrict__ row = reim + (size_t)t * s.ldk;
@@ -442,7 +402,7 @@ void mel_power_log_kernel(const float* __restrict__ reim, const float* __restric
   }
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int m = wave; m < s.n_mels; m += 4) {
+  for (int m = wave; m < n_mels; m += 4) {
     const float* __restrict__ b = mel_basis + (size_t)m * s.F;
     float acc = 0.f;
     for (int f = lane; f < s.F; f += 64) acc = fmaf(b[f], pw[f], acc);
@@ -479,29 +439,29 @@ int vs_speaker_prepare(const vs_speaker_dims* d, const vs_speaker_params* p, voi
   float* header = at<float>(prepared, P.header);
   VS_CHECK_HIP(hipMemsetAsync(header, 0, 64 * 4, stream));
   const long long H4 = 4LL * s.H;
-  hipLaunchKernelGGL(spk_copy_kernel, dim3(grid_for(H4 * s.M)), dim3(256), 0, stream, p->w_ih[0], (const float*)nullptr, at<float>(prepared, P.wih0), H4 * s.M);
+  hipLaunchKernelGGL(spk_copy_kernel, dim3(vs_grid_for(H4 * s.M)), dim3(256), 0, stream, p->w_ih[0], (const float*)nullptr, at<float>(prepared, P.wih0), H4 * s.M);
   for (int l = 0; l < s.L; ++l)
-    hipLaunchKernelGGL(spk_copy_kernel, dim3(grid_for(H4)), dim3(256), 0, stream, p->b_ih[l], p->b_hh[l], at<float>(prepared, P.bias) + l * H4, H4);
-  hipLaunchKernelGGL(spk_copy_kernel, dim3(grid_for((long long)s.E * s.H)), dim3(256), 0, stream, p->proj_w, (const float*)nullptr,
+    hipLaunchKernelGGL(spk_copy_kernel, dim3(vs_grid_for(H4)), dim3(256), 0, stream, p->b_ih[l], p->b_hh[l], at<float>(prepared, P.bias) + l * H4, H4);
+  hipLaunchKernelGGL(spk_copy_kernel, dim3(vs_grid_for((long long)s.E * s.H)), dim3(256), 0, stream, p->proj_w, (const float*)nullptr,
                      at<float>(prepared, P.proj_w), (long long)s.E * s.H);
-  hipLaunchKernelGGL(spk_copy_kernel, dim3(grid_for(s.E)), dim3(256), 0, stream, p->proj_b, (const float*)nullptr, at<float>(prepared, P.proj_b), (long long)s.E);
+  hipLaunchKernelGGL(spk_copy_kernel, dim3(vs_grid_for(s.E)), dim3(256), 0, stream, p->proj_b, (const float*)nullptr, at<float>(prepared, P.proj_b), (long long)s.E);
   if (s.math == VS_MATH_F16X3) {
     for (int l = 0; l < s.L; ++l) {
       const long long nhh = H4 * s.H, nih = l ? nhh : 0;
-      hipLaunchKernelGGL(spk_absmax_kernel, dim3(grid_for(nhh + nih, 256)), dim3(256), 0, stream, p->w_hh[l], nhh, l ? p->w_ih[l] : p->w_hh[l], nih,
+      hipLaunchKernelGGL(spk_absmax_kernel, dim3(vs_grid_for(nhh + nih, 256)), dim3(256), 0, stream, p->w_hh[l], nhh, l ? p->w_ih[l] : p->w_hh[l], nih,
                          reinterpret_cast<unsigned*>(header) + l);
     }
     hipLaunchKernelGGL(spk_scale_kernel, dim3(1), dim3(64), 0, stream, header, s.L);
     for (int l = 0; l < s.L; ++l) {
       const int nkc = layer_k(s, l) / 16;
       const long long total = (long long)s.nub * nkc * 4 * 64 * 8;
-      hipLaunchKernelGGL(spk_pack_f16_kernel, dim3(grid_for(total)), dim3(256), 0, stream, l ? p->w_ih[l] : (const float*)nullptr, p->w_hh[l],
+      hipLaunchKernelGGL(spk_pack_f16_kernel, dim3(vs_grid_for(total)), dim3(256), 0, stream, l ? p->w_ih[l] : (const float*)nullptr, p->w_hh[l],
                          header + 8 + 2 * l, at<_Float16>(prepared, P.w[l]), at<_Float16>(prepared, P.wlo[l]), s.H, s.Hk, nkc, total);
     }
   } else {
     for (int l = 0; l < s.L; ++l) {
       const int Kl = layer_k(s, l);
-      hipLaunchKernelGGL(spk_pack_f32_kernel, dim3(grid_for(H4 * Kl)), dim3(256), 0, stream, l ? p->w_ih[l] : (const float*)nullptr, p->w_hh[l],
+      hipLaunchKernelGGL(spk_pack_f32_kernel, dim3(vs_grid_for(H4 * Kl)), dim3(256), 0, stream, l ? p->w_ih[l] : (const float*)nullptr, p->w_hh[l],
                          at<float>(prepared, P.w[l]), s.H, Kl, H4 * Kl);
     }
   }
@@ -583,21 +543,17 @@ int vs_speaker_embed(const vs_speaker_dims* d, const void* prepared, size_t prep
 }
 
 size_t vs_logmel_workspace_bytes(const vs_loss_dims* d, long long n, int n_mels) {
-  MelShape s;
-  if (mel_shape(d, n, n_mels, &s)) return 0;
-  MelLayout L;
-  mel_layout(s, &L);
-  return L.total;
+  VsStftShape s;
+  return mel_shape(d, n, n_mels, &s) ? 0 : mel_layout(s).total;
 }
 
 int vs_wav_to_logmel(const vs_loss_dims* d, const float* wav, long long n, const float* mel_basis, int n_mels, float* mel,
                      void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  MelShape s;
+  VsStftShape s;
   if (int rc = mel_shape(d, n, n_mels, &s)) return rc;
   VS_REQUIRE(wav && mel_basis && mel && ws, "wav_to_logmel: NULL argument");
-  MelLayout L;
-  mel_layout(s, &L);
+  const MelLayout L = mel_layout(s);
   VS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0 && ws_bytes >= L.total,
              "wav_to_logmel: workspace too small or misaligned (%zu < %zu)", ws_bytes, L.total);
   float* frames = at<float>(ws, L.frames);
@@ -606,13 +562,11 @@ int vs_wav_to_logmel(const vs_loss_dims* d, const float* wav, long long n, const
   unsigned* amax = at<unsigned>(ws, L.amax);
   float* scales = at<float>(ws, L.scales);
   VS_CHECK_HIP(hipMemsetAsync(amax, 0, (size_t)VS_AMAX_SLOTS * 4, stream));
-  hipLaunchKernelGGL(mel_frames_kernel, dim3(grid_for((long long)s.T * s.win)), dim3(256), 0, stream, wav, frames, s, amax);
-  hipLaunchKernelGGL(mel_basis_kernel, dim3((s.K * s.win + 255) / 256), dim3(256), 0, stream, basis, s, scales + 2);
+  vs_stft_frames_launch(wav, frames, s, amax, vs_grid_for((long long)s.T * s.win), stream);
+  vs_stft_basis_launch(basis, s, scales + 2, stream);
   if (int rc = vs_scale_from_absmax_impl(amax, VS_AMAX_SLOTS, scales, stream)) return rc;
-  if (int rc = vs_gemm_f16x3_impl(0, 0, frames, s.win, basis, nullptr, 0x7fffffff, s.win, reim, s.ldk, s.T, s.K, s.win,
-                                  nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, scales, scales + 2, stream,
-                                  VS_MATH_CODE_F16X3)) return rc;
-  hipLaunchKernelGGL(mel_power_log_kernel, dim3(s.T), dim3(256), (size_t)s.F * 4, stream, reim, mel_basis, mel, s);
+  if (int rc = vs_stft_contract(/*split=*/true, 0, frames, s.win, basis, s.win, reim, s.ldk, s.T, s.K, s.win, scales, scales + 2, stream)) return rc;
+  hipLaunchKernelGGL(mel_power_log_kernel, dim3(s.T), dim3(256), (size_t)s.F * 4, stream, reim, mel_basis, mel, s, n_mels);
   VS_LAUNCH_CHECK();
   return 0;
 }

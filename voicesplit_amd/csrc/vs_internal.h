@@ -24,7 +24,7 @@ struct VsTurnScope {
 };
 inline int vs_det_grid(int nb, int cus = 256) { return (g_vs_turn && nb > cus) ? cus : nb; }      // deterministic mode: at most one workgroup per CU takes turns
 
-// ---- host helpers shared by the orchestration files (forward.hip, train.hip, loss.hip, speaker.hip) ----
+// ---- host helpers shared by the orchestration files (forward.hip, train.hip, stft.hip, loss.hip, audio.hip, griffin_lim.hip, speaker.hip) ----
 constexpr float kBnEps = 1e-5f;       // nn.BatchNorm2d default (models/voicesplit/model.py:19)
 constexpr float kBnMomentum = 0.1f;
 // conv-stack table (models/voicesplit/model.py:15-52): KT, KF, time dilation
