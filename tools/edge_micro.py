@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Launch time and effective HBM rate of the memory-side kernels of the channels-last bf16 path (csrc/nhwc_edge.hip) at BASELINE
+"""Launch time and effective HBM rate of the memory-side kernels of the channels-last bf16 path (csrc/nhwc_first.hip, nhwc_bn.hip, nhwc_last.hip) at BASELINE
 size (B = 64, 301 x 601): cnn1 (one-pass forward, input moments, one-pass backward), the BatchNorm apply / backward passes,
 cnn8 forward (on z7, BatchNorm + activation of cnn7 on the way in) and backward (dy form, a7 recomputed)."""
 import json

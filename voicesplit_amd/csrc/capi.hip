@@ -212,7 +212,7 @@ int vs_nhwc_bn_apply(const void* z, void* a, long long npix, int act, const floa
   return vs_nhwc_bn_apply_impl(z, a, npix, act, scale, shift, (hipStream_t)stream);
 }
 
-// cnn1 by recomputation (nhwc_edge.hip)
+// cnn1 by recomputation (nhwc_first.hip)
 int vs_nhwc_first_moments(const float* x, int B, int T, int F, double* moments, void* stream) {
   return vs_nhwc_first_moments_impl(x, B, T, F, moments, (hipStream_t)stream);
 }

@@ -452,7 +452,7 @@ int vs_bn_apply_feat_bf16_impl(const float* x, float* y, void* yb, int Kp, int B
   VS_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(yb) & 15) == 0,
              "bn_apply_feat_bf16: buffers must be 16-byte aligned");
   const long long rows = (long long)B * T, total = rows * (Kp >> 3);
-  // [r6, call 31] one sweep (a workgroup per 256 pieces, no grid-stride loop): 212 -> 177 us at B = 64 (nhwc_edge.hip: stream_blocks_wide)
+  // [r6, call 31] one sweep (a workgroup per 256 pieces, no grid-stride loop): 212 -> 177 us at B = 64 (nhwc_common.h: stream_blocks_wide)
   const int ga = (int)((total + 255) / 256 < (1LL << 24) ? (total + 255) / 256 : (1LL << 24));
   unsigned short* o = reinterpret_cast<unsigned short*>(yb);
   switch (act) {

@@ -316,7 +316,7 @@ bool cnn8_writes_gemm_operand(const Fwd& f) {
 }
 
 // BASELINE configs[2]: channels-last bf16 activations [B][T][F][64] in the ping-pong buffers (half their size), conv_nhwc.hip /
-// nhwc_edge.hip kernels.  eval: BatchNorm + activation in the conv epilogue; train: z = conv + bias with statistics from the
+// nhwc_first.hip / nhwc_bn.hip / nhwc_last.hip kernels.  eval: BatchNorm + activation in the conv epilogue; train: z = conv + bias with statistics from the
 // epilogue, then one apply pass in place.
 int convs_nhwc_bf16(const Fwd& f, const float* x, float* feat, bool rows) {
   const vs_params* p = f.p;
@@ -331,7 +331,7 @@ int convs_nhwc_bf16(const Fwd& f, const float* x, float* feat, bool rows) {
     const vs_conv_layer& cl = p->conv[0];
     const BnPair k = f.bn(0);
     if (f.train) {
-      // cnn1 by recomputation (nhwc_edge.hip): statistics of z1 from the input's moments, then one pass that writes act(BN(z1))
+      // cnn1 by recomputation (nhwc_first.hip): statistics of z1 from the input's moments, then one pass that writes act(BN(z1))
       double* mom = stats + 128;                          // behind slot 0 of the statistics scratch
       if (int rc = vs_nhwc_first_moments_impl(x, B, T, F, mom, f.stream)) return rc;
       if (int rc = vs_nhwc_first_stats_impl(mom, cl.weight, cl.bias, (double)npix, stats, f.stream)) return rc;

@@ -96,7 +96,7 @@ __global__ void cvt_f64_f32_kernel(const double* __restrict__ src, float* __rest
 
 }  // namespace
 
-// dst[i] = (float)src[i]: the fp64 accumulators of cnn1's weight gradient (conv_bwd.hip, nhwc_edge.hip)
+// dst[i] = (float)src[i]: the fp64 accumulators of cnn1's weight gradient (conv_bwd.hip, nhwc_first.hip)
 int vs_cvt_f64_f32_impl(const double* src, float* dst, int n, hipStream_t stream) {
   hipLaunchKernelGGL(cvt_f64_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, src, dst, n);
   VS_LAUNCH_CHECK();

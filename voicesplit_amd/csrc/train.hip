@@ -307,7 +307,7 @@ int weight_images(const Step& st, const float* dvec, hipStream_t s) {
 }
 
 // cnn1 of the bf16 configuration, by recomputation: the batch statistics of z1 = conv(x) + bias from the 35 moments of the input's
-// seven shifts (one pass over the 46 MB input), then ONE pass that writes a1 = act(BN(z1)): no z1 tensor, no apply pass (nhwc_edge.hip)
+// seven shifts (one pass over the 46 MB input), then ONE pass that writes a1 = act(BN(z1)): no z1 tensor, no apply pass (nhwc_first.hip)
 int cnn1_nhwc(const Step& st, const float* x) {
   VsProfScope ps(VS_PROF_CNN1, st.stream);
   const vs_conv_layer& c = st.p->conv[0];
@@ -327,7 +327,7 @@ int cnn1_nhwc(const Step& st, const float* x) {
   return vs_nhwc_conv_first_impl(x, c.weight, k.scale, k.shift, st.at<void>(st.L.a[0]), st.B, st.T, st.F, st.conv_act, nullptr, st.stream, c.bias);
 }
 
-// cnn2 .. cnn8 on channels-last bf16 z / a (conv_nhwc.hip, nhwc_edge.hip); statistics from the conv epilogues
+// cnn2 .. cnn8 on channels-last bf16 z / a (conv_nhwc.hip, nhwc_bn.hip, nhwc_last.hip); statistics from the conv epilogues
 int convs_nhwc(const Step& st) {
   const vs_params* p = st.p;
   const vs_tape_layout& L = st.L;
@@ -676,7 +676,7 @@ int features_bn_bwd(const Step& st, const vs_grads* g) {
                             g->conv[7].bn_weight, g->conv[7].bn_bias, g->conv[7].bias, st.stats, st.coef, nullptr, st.stream);
 }
 
-// BASELINE configs[2]: cnn8 .. cnn1 backward on channels-last bf16 tensors (nhwc_edge.hip, conv_nhwc.hip, wgrad_nhwc.hip).
+// BASELINE configs[2]: cnn8 .. cnn1 backward on channels-last bf16 tensors (nhwc_last.hip, nhwc_bn.hip, nhwc_first.hip, conv_nhwc.hip, wgrad_nhwc.hip).
 // Every kernel that produces a layer's input gradient (cnn8's backward, the data-gradient convs) applies the activation derivative of
 // the layer below on the spot and accumulates the BatchNorm backward sums (the dy forms): the BatchNorm backward proper is then
 // finalize + one pass (see kBwdFinalizeClearsDoubles for the memsets).

@@ -134,7 +134,7 @@ int vs_nhwc_f16x3_layer_impl(const void* in_hi, const void* in_lo, const float* 
                              const float* w, const float* bn_scale, const float* bn_shift, void* wpart, int packed_ready, float* plan,
                              void* out_hi, void* out_lo, float* out_scale2, unsigned* amax_out,
                              int B, int T, int F, int KT, int KF, int dil, int act, hipStream_t);
-// nhwc_edge.hip: cnn1 / cnn8 on the same planes
+// nhwc_first.hip / nhwc_last.hip: cnn1 / cnn8 on the same planes
 int vs_absmax_any_impl(const float* x, long long n, unsigned* amax, hipStream_t);
 int vs_nhwc_first_plan_impl(const unsigned* amax_in, int n_amax, const float* w, const float* scale, const float* shift, float* out_scale2, hipStream_t);
 int vs_nhwc_conv_first_split_impl(const float* x, const float* w, const float* scale, const float* shift, const float* out_scale2,
@@ -148,11 +148,11 @@ int vs_nhwc_conv_last_split_impl(const void* in_hi, const void* in_lo, const flo
 #define VS_NHWC_WGRAD_MAX_PAIRS 128
 size_t vs_nhwc_wgrad_partial_floats(int KT, int KF);
 int vs_nhwc_wgrad_impl(const void* dz, const void* a_in, float* part, float* dw, int B, int T, int F, int KT, int KF, int dil, hipStream_t);
-// nhwc_edge.hip: the HBM-bound kernels around them (cnn1, BatchNorm apply, cnn8)
+// nhwc_first.hip, nhwc_bn.hip, nhwc_last.hip: the HBM-bound kernels around them (cnn1, BatchNorm apply, cnn8)
 int vs_nhwc_conv_first_impl(const float* x, const float* w, const float* scale, const float* shift, void* out,
                             int B, int T, int F, int act, double* bn_stats, hipStream_t,
                             const float* bias = nullptr /* scale / shift are BatchNorm constants of conv + bias */);
-// cnn1 by recomputation (nhwc_edge.hip): input moments -> batch statistics of z1; one-pass backward
+// cnn1 by recomputation (nhwc_first.hip): input moments -> batch statistics of z1; one-pass backward
 #define VS_FIRST_MOMENTS 35
 #define VS_FIRST_BWD_SCRATCH_DOUBLES (64 * 9 + VS_FIRST_MOMENTS)
 int vs_nhwc_first_moments_impl(const float* x, int B, int T, int F, double* mom, hipStream_t, double* det_slots = nullptr, int mom_is_zero = 0);
