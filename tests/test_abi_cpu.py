@@ -223,3 +223,67 @@ def test_tensor_index_follows_the_module_tree_and_transients_stay_out_of_copies(
     assert "_grad_sink" in m.__dict__
     m.set_gradient_sink(None)
     assert "_grad_sink" not in m.__dict__
+
+
+# ---- the STFT entry points: geometries the library refuses, and the envelope cache -------------------------------------------
+def _loss_dims(n_fft, hop, win, F=None, B=2, T=9):
+    from voicesplit_amd import _lib
+    return _lib.VsLossDims(B, T, n_fft // 2 + 1 if F is None else F, n_fft, hop, win, -100.0, 20.0)
+
+
+def _stft_calls():
+    """name -> call(dims, ws_bytes) -> (rc, message).  Every pointer is a dummy that is never dereferenced: each call of the tests
+    below is refused before any device work."""
+    from voicesplit_amd import _lib
+    lib = _lib.load()
+    p, ws = ctypes.c_void_p(4096), ctypes.c_void_p(1 << 20)
+    big = 1 << 40
+
+    def answer(rc):
+        return rc, lib.vs_last_error()
+
+    return lib, {
+        "vs_sisnr_workspace_bytes": lambda d, n=big: answer(0 if lib.vs_sisnr_workspace_bytes(ctypes.byref(d)) else -1),
+        "vs_sisnr_loss": lambda d, n=big: answer(lib.vs_sisnr_loss(ctypes.byref(d), p, p, p, p, None, ws, n, p, None, None, None)),
+        "vs_spec_to_wav": lambda d, n=big: answer(lib.vs_spec_to_wav(ctypes.byref(d), p, None, p, p, ws, n, None)),
+        "vs_wav_to_spec": lambda d, n=big: answer(lib.vs_wav_to_spec(ctypes.byref(d), p, p, p, ws, n, None)),
+        "vs_wav_to_logmel": lambda d, n=big: answer(lib.vs_wav_to_logmel(ctypes.byref(d), p, 4000, p, 40, p, ws, n, None)),
+    }
+
+
+@pytest.mark.parametrize("name", ["vs_sisnr_workspace_bytes", "vs_spec_to_wav", "vs_wav_to_spec", "vs_wav_to_logmel"])
+def test_stft_entry_points_refuse_a_geometry_they_cannot_serve(name):
+    """hop > win, win > n_fft and F != n_fft / 2 + 1: a non-zero return (0 bytes from the size function) and the message that
+    names the rule, from every entry point that takes a vs_loss_dims."""
+    _lib_, calls = _stft_calls()
+    call = calls[name]
+    for dims, text in ((_loss_dims(64, 17, 16), b"need hop <= win <= n_fft"),
+                       (_loss_dims(64, 16, 65), b"need hop <= win <= n_fft"),
+                       (_loss_dims(64, 16, 64, F=32), b"must be n_fft/2+1"),
+                       (_loss_dims(64, 16, 64, F=34), b"must be n_fft/2+1")):
+        rc, msg = call(dims)
+        assert rc != 0 and text in msg, (name, dims.n_fft, dims.hop, dims.win, dims.F, rc, msg)
+    # the limits themselves are legal: hop == win == n_fft passes the shape rules (what refuses it next is the envelope, below)
+    assert _lib_.vs_sisnr_workspace_bytes(ctypes.byref(_loss_dims(64, 64, 64))) > 0
+
+
+def test_no_overlap_is_refused_and_the_envelope_cache_follows_the_geometry():
+    """hop == win leaves samples under a zero of the Hann window: vs_spec_to_wav (periodic window) and vs_sisnr_loss (symmetric)
+    refuse it with "envelope".  vs_stft_check_envelope keeps the last shape's minimum in a thread-local cache keyed on (hop, win, T,
+    periodic); three calls in a row that end at the workspace check when the envelope check has passed show that the cache is
+    invalidated in both directions."""
+    _lib_, calls = _stft_calls()
+    bad, good = _loss_dims(64, 64, 64), _loss_dims(64, 16, 64)
+    for name in ("vs_spec_to_wav", "vs_sisnr_loss"):
+        rc, msg = calls[name](bad)
+        assert rc != 0 and b"envelope" in msg and b"hop=64 win=64" in msg, (name, msg)
+    for dims, text in ((good, b"workspace too small"), (bad, b"envelope"), (good, b"workspace too small"), (good, b"workspace too small")):
+        rc, msg = calls["vs_spec_to_wav"](dims, 256)
+        assert rc != 0 and text in msg, (dims.hop, msg)
+    # the same T and hop with another window, and the two window forms of one geometry, are different cache entries
+    rc, msg = calls["vs_spec_to_wav"](_loss_dims(64, 16, 16), 256)
+    assert rc != 0 and b"envelope" in msg and b"periodic" in msg
+    rc, msg = calls["vs_sisnr_loss"](_loss_dims(64, 16, 16), 256)
+    assert rc != 0 and b"envelope" in msg and b"symmetric" in msg
+    rc, msg = calls["vs_sisnr_loss"](good, 256)
+    assert rc != 0 and b"workspace too small" in msg

@@ -26,6 +26,9 @@ def _case(B, T, n_fft, hop, win, seed, lens=None, mixed_gain=1.0):
     (3, 12, 40, 8, 16, [88, 50, 70], 1.3),        # ragged lengths, some mixed*mask above the clamp
     (1, 5, 64, 16, 64, None, 1.0),                # window as wide as the frame
     (2, 21, 1200, 160, 400, [3200, 2500], 1.0),   # the reference's STFT geometry, short clip
+    (2, 4, 64, 11, 64, None, 1.0),                # odd hop that does not divide the window (6 frames per sample); w[0] = w[63] = 0 under the envelope
+    (2, 12, 402, 100, 200, [1100, 700], 1.3),     # n_fft = 2 (mod 4): K = 2 F = 404, no row padding; hop = win / 2
+    (1, 7, 256, 64, 255, None, 1.0),              # odd window one short of the frame; win % 4 != 0
 ])
 def test_sisnr_loss_and_mask_gradient(B, T, n_fft, hop, win, lens, gain):
     from voicesplit_amd import losses

@@ -315,11 +315,12 @@ def _audio_legs_per_clip(wav, cfg, mask_seed):
     out_m = audio.spec_to_wav(spec, phase, cfg, mask=mask).cpu().double().numpy()
     out_1 = audio.spec_to_wav(spec, phase, cfg).cpu().double().numpy()
     spec_c, phase_c, mask_c = spec.cpu(), phase.cpu(), mask.cpu()
-    lin = lambda s_: np.power(10.0, ((s_ - 1.0) * 100.0 + 20.0) / 20.0)
+    min_db, ref_db = float(cfg["min_level_db"]), float(cfg["ref_level_db"])
+    lin = lambda s_: np.power(10.0, ((s_ - 1.0) * -min_db + ref_db) / 20.0)
     table, bad = [], []
     for b in range(B):
         x = wav[b].double().numpy()
-        rs, rp = RA.wav2spec(x, cfg["n_fft"], hop, win)
+        rs, rp = RA.wav2spec(x, cfg["n_fft"], hop, win, min_db, ref_db)
         mag = np.abs(RA.stft(x, cfg["n_fft"], hop, win)).T
         got_s, ph_b = spec_c[b].double().numpy(), phase_c[b].double().numpy()
         got, ref = lin(got_s), lin(rs)
@@ -327,8 +328,8 @@ def _audio_legs_per_clip(wav, cfg, mask_seed):
         med = np.median(np.abs(got_s - rs))
         strong = mag > 1e-2 * mag.max()
         ph = np.abs(np.angle(np.exp(1j * (ph_b - rp))))[strong].max()
-        ref_m = RA.spec2wav((spec_c[b] * mask_c[b]).double().numpy(), ph_b, hop, win)
-        ref_1 = RA.spec2wav(got_s, ph_b, hop, win)
+        ref_m = RA.spec2wav((spec_c[b] * mask_c[b]).double().numpy(), ph_b, hop, win, min_db, ref_db)
+        ref_1 = RA.spec2wav(got_s, ph_b, hop, win, min_db, ref_db)
         em = np.abs(out_m[b] - ref_m).max() / np.abs(ref_m).max()
         e1 = np.abs(out_1[b] - ref_1).max() / np.abs(ref_1).max()
         row = dict(clip=b, spec_max=float(rs.max()), lin_ratio=float(lin_ratio), median=float(med), phase=float(ph),

@@ -169,15 +169,16 @@ def test_large_batch_every_row_equals_its_batch_of_32_and_a_rerun():
     assert worst <= BOUND
 
 
-def _stft_power(wav, dtype):
-    """|librosa.stft(n_fft 1200, hop 160, win 400, hann, center, reflect)|^2 restated with torch.stft on the reflect-padded signal:
-    periodic Hann of 400 centred in 1200."""
+def _stft_power(wav, dtype, n_fft=1200, hop=160, win=400):
+    """|librosa.stft(n_fft, hop, win, hann, center, reflect)|^2 restated with torch.stft on the reflect-padded signal:
+    periodic Hann of ``win`` zero-padded to n_fft at offset (n_fft - win) // 2 (1200 / 160 / 400: 400 centred in 1200)."""
     x = wav.to(dtype)
-    pad = torch.nn.functional.pad(x[None, None], (600, 600), mode="reflect")[0, 0]
-    win = torch.zeros(1200, dtype=dtype)
-    win[400:800] = torch.hann_window(400, periodic=True, dtype=dtype)
-    D = torch.stft(pad, 1200, hop_length=160, win_length=1200, window=win, center=False, return_complex=True)
-    return D.real ** 2 + D.imag ** 2          # [601, T]
+    pad = torch.nn.functional.pad(x[None, None], (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
+    lo = (n_fft - win) // 2
+    window = torch.zeros(n_fft, dtype=dtype)
+    window[lo:lo + win] = torch.hann_window(win, periodic=True, dtype=dtype)
+    D = torch.stft(pad, n_fft, hop_length=hop, win_length=n_fft, window=window, center=False, return_complex=True)
+    return D.real ** 2 + D.imag ** 2          # [n_fft / 2 + 1, T]
 
 
 def test_logmel_against_fp64_restatement():
@@ -209,8 +210,9 @@ def test_logmel_against_fp64_restatement():
 
 @pytest.mark.parametrize("n", [601, 800, 1237])
 def test_logmel_short_clips_against_fp64_restatement(n):
-    """The shortest legal clip (n_fft / 2 + 1 samples: both reflections reach across the whole clip), a multiple of the hop and a
-    non-multiple, cut from demo clip 0 at sample 16000 (largest mel power of the three slices 6.5 .. 9.4: speech, not a pause).
+    """The shortest legal clip (n_fft / 2 + 1 samples; the 400-sample window reaches only 200 samples past a clip edge, so neither
+    reflection is at its limit here: test_logmel_other_geometries_against_fp64_restatement has that case), a multiple of the hop
+    and a non-multiple, cut from demo clip 0 at sample 16000 (largest mel power of the three slices 6.5 .. 9.4: speech, not a pause).
     The linear criterion of test_logmel_against_fp64_restatement, same bound."""
     from voicesplit_amd import logmel, mel_filterbank
     w = demo_wavs()[0][16000:16000 + n].contiguous()
@@ -220,6 +222,32 @@ def test_logmel_short_clips_against_fp64_restatement(n):
     assert P_ref.max().item() > 1e-3
     lin = ((10.0 ** got - 1e-6) - P_ref).abs().max().item() / P_ref.max().item()
     print(f"logmel n={n}: linear {lin:.2e}")
+    assert lin <= BOUND
+
+
+@pytest.mark.parametrize("n_fft,hop,win,sr,mels,n", [
+    (1024, 256, 1024, 22050, 80, 513),       # win == n_fft at the shortest legal clip: both reflections reach across the whole clip
+    (1024, 256, 1024, 22050, 80, 1237),      # no multiple of the hop
+    (256, 64, 255, 16000, 20, 129),          # odd window one short of the frame (lead 128), the shortest legal clip
+    (256, 64, 255, 16000, 20, 300),
+])
+def test_logmel_other_geometries_against_fp64_restatement(n_fft, hop, win, sr, mels, n):
+    """The linear criterion of test_logmel_short_clips_against_fp64_restatement, same bound, at the reference's waveglow block
+    (1024 / 256 / 1024, 80 mels at 22050 Hz) and at 256 / 64 / 255 with 20 mels: the shortest legal clip n = n_fft / 2 + 1, where,
+    once the window is as wide as the frame, the first frame's reflection lands exactly on sample n - 1 and the last frame's
+    (centred on sample n - 1 here) on sample 1, and a length that is no multiple of the hop.  Neither filter bank has an empty row
+    (asserted)."""
+    from voicesplit_amd import logmel, mel_filterbank
+    cfg = dict(AUDIO, n_fft=n_fft, num_freq=n_fft // 2 + 1, hop_length=hop, win_length=win, sample_rate=sr)
+    fb = mel_filterbank(sr, n_fft, mels)
+    assert fb.shape == (mels, n_fft // 2 + 1) and (fb.sum(dim=1) > 0).all()
+    w = demo_wavs()[0][16000:16000 + n].contiguous()
+    got = logmel(w.to(DEV), cfg, mels).double().cpu()
+    P_ref = fb.double() @ _stft_power(w, torch.float64, n_fft, hop, win)
+    assert got.shape == P_ref.shape == (mels, 1 + n // hop)
+    assert P_ref.max().item() > 1e-3
+    lin = ((10.0 ** got - 1e-6) - P_ref).abs().max().item() / P_ref.max().item()
+    print(f"logmel {n_fft}/{hop}/{win} mels={mels} n={n}: linear {lin:.2e}")
     assert lin <= BOUND
 
 

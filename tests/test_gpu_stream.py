@@ -358,3 +358,78 @@ def test_streaming_separator_equals_the_whole_clip_synthesis(math):
             assert worst < sep.latency_samples
             if sizes == (1,):          # hop by hop: every block after the first starts exactly latency_samples behind the newest sample
                 assert at_emission == {sep.latency_samples} and worst == sep.latency_samples - hop
+
+
+# ---- the separator where hop divides n_fft / 2 -----------------------------------------------------------------------------------
+_SMALL = {}
+
+
+def _small(n_fft):
+    """A VoiceSplit with num_freq = fc2_dim = n_fft / 2 + 1 (lstm_dim 24: a width of RAW_SHAPES) and two d-vectors, built once."""
+    if n_fft not in _SMALL:
+        import voicesplit_amd as V
+        dims = dict(num_freq=n_fft // 2 + 1, emb_dim=16, lstm_dim=24, fc1_dim=40, fc2_dim=n_fft // 2 + 1)
+        m = V.VoiceSplit(V.default_config(**dims)).eval()
+        m.load_state_dict(R.spread_logits(R.build_state_dict(dims, 2), 6.0))
+        _SMALL[n_fft] = (m.cuda(), R.synthetic_inputs(2, 8, dims, 2)[1].cuda())
+    return _SMALL[n_fft]
+
+
+@pytest.mark.parametrize("n_fft,hop,win", [(64, 16, 64), (256, 64, 255)], ids=["64-16-64", "256-64-255"])
+def test_streaming_separator_where_hop_divides_half_the_frame(n_fft, hop, win):
+    """The body of test_streaming_separator_equals_the_whole_clip_synthesis at 64 / 16 / 64 and 256 / 64 / 255 (an odd window), C = 4,
+    R = 2, 160 hops.  Here margin * hop == n_fft / 2 exactly, so the segment pending when the stream reaches ``margin`` hops is
+    as long as the reflect padding and vs_wav_to_spec refuses it: the separator must hold the first analysis back until more
+    than n_fft / 2 samples are pending.  The uneven pushes start with exactly ``margin`` hops; the hop-sized ones reach it at push
+    number ``margin``."""
+    from voicesplit_amd import audio
+    cfg = dict(AUDIO, n_fft=n_fft, hop_length=hop, win_length=win)
+    model, dvec = _small(n_fft)
+    S, C, Rl, margin = 160 * hop, 4, 2, n_fft // 2 // hop
+    assert margin * hop == n_fft // 2
+    wav = _wav(2, S, 6).cuda()
+    spec, phase = audio.wav_to_spec(wav, cfg)
+    for tag, sizes in (("uneven pushes", (margin, 40, 1, 17, 9)), ("hop-sized pushes", (1,))):
+        sep = audio.StreamingSeparator(model, dvec, cfg, C, Rl, trace=True)
+        assert sep.margin == margin and sep.latency_samples == (C + Rl + 65 + 2 * margin) * hop
+        outs, pos, i, worst, at_emission, blocks = [], 0, 0, 0, set(), 0
+        while pos < S:
+            n = min(sizes[i % len(sizes)] * hop, S - pos)
+            returned = sum(o.shape[1] for o in outs)
+            out = sep.push(wav[:, pos:pos + n].contiguous())
+            pos, i = pos + n, i + 1
+            if out.shape[1] and returned:
+                at_emission.add(pos - returned)
+            blocks += bool(out.shape[1])
+            outs.append(out)
+            worst = max(worst, pos - returned - out.shape[1])
+        outs.append(sep.finish())
+        got = torch.cat(outs, dim=1)
+        masks = torch.cat(sep.mask_trace, dim=1)
+        assert got.shape == (2, S) and masks.shape == spec.shape          # every pushed sample is returned
+        ref = audio.spec_to_wav(spec, phase, cfg, mask=masks.contiguous())
+        err = ((got - ref).abs().max() / ref.abs().max()).item()
+        print(f"{n_fft}/{hop}/{win} {tag}: max |streamed - whole-clip synthesis| / max |whole| = {err:.3e} (bound {WAV_TOL:.0e}); "
+              f"{blocks} blocks before finish(), a block starts {sorted(at_emission)} samples behind the newest one, at most {worst} "
+              f"stay withheld behind a push, reported latency {sep.latency_samples}")
+        assert blocks >= 3                                                 # several chunks came out while the stream ran
+        assert err < WAV_TOL
+        assert worst < sep.latency_samples
+        if sizes == (1,):
+            assert at_emission == {sep.latency_samples} and worst == sep.latency_samples - hop
+
+
+def test_streaming_separator_finish_on_a_stream_no_longer_than_the_reflect_padding():
+    """A stream that ends with n_fft / 2 samples or fewer: push() holds them back and returns nothing, finish() raises what the
+    whole-clip call raises, VoiceSplitHipError."""
+    from voicesplit_amd import _lib, audio
+    cfg = dict(AUDIO, n_fft=64, hop_length=16, win_length=64)
+    model, dvec = _small(64)
+    wav = _wav(2, 32, 7).cuda()
+    with pytest.raises(_lib.VoiceSplitHipError, match="reflect padding"):
+        audio.wav_to_spec(wav, cfg)
+    sep = audio.StreamingSeparator(model, dvec, cfg, 4, 2)
+    for k in range(2):
+        assert sep.push(wav[:, 16 * k:16 * (k + 1)].contiguous()).shape == (2, 0)
+    with pytest.raises(_lib.VoiceSplitHipError, match="reflect padding"):
+        sep.finish()

@@ -274,3 +274,89 @@ def test_module_surface_and_train_mode_refusal():
 def _lib_error():
     from voicesplit_amd import _lib
     return _lib.VoiceSplitHipError
+
+
+# ---- audio.StreamingSeparator's host arithmetic, with fp64 transforms standing in for the two device legs ------------------------
+class _FrameModel:
+    """stream_stages() of a mask that depends on the frame alone, so the streamed masks are the whole clip's whatever the chunks."""
+
+    def stream_stages(self):
+        return (lambda x: x, lambda feat, dvec, state, keep: (torch.cat((feat, feat), dim=2), state),
+                lambda lstm_out: torch.sigmoid(4.0 * lstm_out[..., :lstm_out.shape[2] // 2] - 2.0))
+
+
+def _fp64_legs(monkeypatch):
+    """audio.wav_to_spec / spec_to_wav answered by oracle.reference_audio per clip, with the library's refusal of a segment that
+    is not longer than the reflect padding; returns the list of segment lengths the separator asked for."""
+    import numpy as np
+    from oracle import reference_audio as RA
+    from voicesplit_amd import audio
+    asked = []
+
+    def wav_to_spec(wav, cfg, want_phase=True):
+        n_fft, hop, win = int(cfg["n_fft"]), int(cfg["hop_length"]), int(cfg["win_length"])
+        asked.append(wav.shape[1])
+        if wav.shape[1] <= n_fft // 2:
+            raise _lib_error()("vs_wav_to_spec failed (rc=-1): wav_to_spec: clip shorter than the reflect padding")
+        out = [RA.wav2spec(w.numpy(), n_fft, hop, win) for w in wav.double()]
+        return (torch.from_numpy(np.stack([o[0] for o in out])), torch.from_numpy(np.stack([o[1] for o in out])))
+
+    def spec_to_wav(spec, phase, cfg, mask=None):
+        v = spec if mask is None else spec * mask
+        return torch.from_numpy(np.stack([RA.spec2wav(s.numpy(), p.numpy(), int(cfg["hop_length"]), int(cfg["win_length"]))
+                                          for s, p in zip(v, phase)]))
+
+    monkeypatch.setattr(audio, "wav_to_spec", wav_to_spec)
+    monkeypatch.setattr(audio, "spec_to_wav", spec_to_wav)
+    return asked
+
+
+@pytest.mark.parametrize("n_fft,hop,win", [(1200, 160, 400), (64, 16, 64), (256, 64, 255), (64, 11, 64), (64, 32, 64), (402, 100, 200)])
+@pytest.mark.parametrize("sizes", [(1,), (2, 40, 1, 17, 9), (1, 1, 3, 200)])
+def test_separator_glue_returns_the_whole_clip_synthesis_at_every_geometry(monkeypatch, n_fft, hop, win, sizes):
+    """Where hop divides n_fft / 2 (64 / 16, 256 / 64, 64 / 32) ``margin`` hops are exactly as long as the reflect padding: the
+    separator must not hand such a segment to wav_to_spec, neither at the start of the stream nor at finish().  In fp64 the streamed
+    output is the whole-clip synthesis with the streamed masks to rounding, every pushed sample comes back, and nothing stays
+    withheld longer than latency_samples."""
+    from voicesplit_amd import audio
+    asked = _fp64_legs(monkeypatch)
+    cfg = {"n_fft": n_fft, "hop_length": hop, "win_length": win, "min_level_db": -100.0, "ref_level_db": 20.0}
+    C, Rl, hops = 4, 2, 110
+    S = hops * hop
+    g = torch.Generator().manual_seed(n_fft + hop)
+    wav = 0.1 * torch.randn(2, S, generator=g, dtype=torch.float64)
+    spec, phase = audio.wav_to_spec(wav, cfg)
+    sep = audio.StreamingSeparator(_FrameModel(), torch.zeros(2, 4), cfg, C, Rl, trace=True)
+    assert sep.latency_samples == (C + Rl + 65 + 2 * -(-(n_fft // 2) // hop)) * hop
+    del asked[:]
+    outs, pos, i, worst, at_emission = [], 0, 0, 0, set()
+    while pos < S:
+        n = min(sizes[i % len(sizes)] * hop, S - pos)
+        returned = sum(o.shape[1] for o in outs)
+        out = sep.push(wav[:, pos:pos + n].contiguous())
+        pos, i = pos + n, i + 1
+        if out.shape[1] and returned:
+            at_emission.add(pos - returned)
+        outs.append(out)
+        worst = max(worst, pos - returned - out.shape[1])
+    outs.append(sep.finish())
+    got, masks = torch.cat(outs, dim=1), torch.cat(sep.mask_trace, dim=1)
+    assert got.shape == (2, S) and masks.shape == spec.shape
+    assert (masks - torch.sigmoid(4.0 * spec - 2.0)).abs().max().item() < 1e-12      # every frame analysed exactly: the whole clip's spectrogram
+    ref = audio.spec_to_wav(spec, phase, cfg, mask=masks)
+    assert ((got - ref).abs().max() / ref.abs().max()).item() < 1e-12
+    assert asked and min(asked) > n_fft // 2 and worst < sep.latency_samples
+    if sizes == (1,):
+        assert at_emission == {sep.latency_samples} and worst == sep.latency_samples - hop
+
+
+def test_separator_glue_on_a_stream_no_longer_than_the_reflect_padding(monkeypatch):
+    from voicesplit_amd import audio
+    asked = _fp64_legs(monkeypatch)
+    cfg = {"n_fft": 64, "hop_length": 16, "win_length": 64, "min_level_db": -100.0, "ref_level_db": 20.0}
+    sep = audio.StreamingSeparator(_FrameModel(), torch.zeros(1, 4), cfg, 4, 2)
+    for _ in range(2):
+        assert sep.push(torch.zeros(1, 16, dtype=torch.float64)).shape == (1, 0)
+    assert asked == []                                                     # 32 samples pending: nothing to transform yet
+    with pytest.raises(_lib_error(), match="reflect padding"):
+        sep.finish()

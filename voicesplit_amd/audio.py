@@ -205,7 +205,10 @@ class StreamingSeparator:
 
     * STFT: the pending samples are transformed as one segment; its reflect padding reaches ``margin = ceil(n_fft / 2 / hop)``
       frames in from each end, so frames that close to a segment edge that is not a stream edge are dropped, and the samples
-      they need are kept and transformed again with the next segment;
+      they need are kept and transformed again with the next segment.  ``wav_to_spec`` takes a segment only if it is longer
+      than n_fft / 2 samples, so a segment has at least ``hold = n_fft / 2 // hop + 1`` hops: ``margin`` of them, or one more
+      where hop divides n_fft / 2 and ``margin`` hops are exactly as long as the padding.  Until the stream has ``hold`` hops no
+      frame is taken, and that many hops are kept in front of the first frame still to come;
     * iSTFT: the masked frames are inverted as one segment; the overlap-add of a sample within ``margin`` frames of a segment
       edge that is not a stream edge misses frames, so those samples are dropped and their frames are inverted again later.
 
@@ -217,6 +220,7 @@ class StreamingSeparator:
         self.cfg = audio_cfg
         self.hop = int(audio_cfg["hop_length"])
         self.margin = -(-(int(audio_cfg["n_fft"]) // 2) // self.hop)
+        self.hold = int(audio_cfg["n_fft"]) // 2 // self.hop + 1      # the fewest hops wav_to_spec takes: hold * hop > n_fft / 2
         self.masker = StreamingMasker(*model.stream_stages(), dvec, C, R)
         self.finished = False
         self._wav, self._w0 = None, 0            # samples from frame _w0 (sample _w0 * hop) on
@@ -230,7 +234,9 @@ class StreamingSeparator:
     @property
     def latency_samples(self) -> int:
         """A returned block starts ``latency_samples`` behind the newest pushed sample: frames the STFT holds back (margin), the
-        masker's chunk, look-ahead and conv halo, and the frames the iSTFT holds back (margin + the frame that closes a hop)."""
+        masker's chunk, look-ahead and conv halo, and the frames the iSTFT holds back (margin + the frame that closes a hop).
+        Where the first analysis waits for one hop more than ``margin`` (see ``hold``) the frames it withheld arrive with that hop,
+        long before the masker's first chunk is due, so the bound is the same."""
         return (self.masker.latency_frames + 2 * self.margin) * self.hop
 
     def push(self, samples: torch.Tensor) -> torch.Tensor:
@@ -252,8 +258,11 @@ class StreamingSeparator:
 
     def _advance(self) -> torch.Tensor:
         m, hop = self.margin, self.hop
-        # analysis: frames [_frames, n_valid) are exact now
-        n_valid = self._hops + 1 if self.finished else max(0, self._hops - m + 1)
+        # analysis: frames [_frames, n_valid) are exact now (a segment of fewer than hold hops is too short to transform: wait)
+        if self.finished:
+            n_valid = self._hops + 1
+        else:
+            n_valid = max(0, self._hops - m + 1) if self._hops - self._w0 >= self.hold else self._frames
         masks = []
         if n_valid > self._frames and self._hops > self._w0:
             spec, phase = wav_to_spec(self._wav.contiguous(), self.cfg)                  # frames [_w0, _hops]
@@ -262,7 +271,7 @@ class StreamingSeparator:
             self._spec = spec if self._spec is None else torch.cat((self._spec, spec), dim=1)
             self._phase = phase if self._phase is None else torch.cat((self._phase, phase), dim=1)
             self._frames = n_valid
-            w0 = max(0, self._frames - m)
+            w0 = max(0, self._frames - self.hold)
             self._wav, self._w0 = self._wav[:, (w0 - self._w0) * hop:], w0
             masks.append(self.masker.push(spec.contiguous()))
         if self.finished and self._frames:
