@@ -546,7 +546,9 @@ int vs_set_wgrad_kernel(int mode);
 /* which 5x5 split-f16 forward / data-gradient kernel vs_conv64_f16x3_fwd and the whole-path calls
  * launch: 0 = default (the persistent pipelined kernel, csrc/conv_f16x3_pk.hip), 1 = one tile per
  * workgroup (csrc/conv_f16x3.hip), 2 = persistent.  Both give bit-identical results (same K order);
- * the switch exists for A/B timing and the bitwise cross-check.  Process-wide. */
+ * the switch exists for A/B timing and the bitwise cross-check.  Process-wide; returns -1 for any other mode and keeps
+ * the current one.  (The timing ablations of the persistent kernel are instances of `make ABLATION=1` libraries, selected by
+ * mode 2 + VS_OPT_ABLATION.) */
 int vs_set_conv_kernel(int mode);
 /* which BiLSTM recurrence / BPTT runs: 0 = default (the persistent kernels whenever all their workgroups
  * fit on the device at once, else one launch per time step), 1 = one launch per step (always the fp32 MFMA products),
@@ -580,10 +582,11 @@ enum vs_option {
                                  kernel (in-flight conversion).  Default 1.  Same operand roundings, fp32 summation order differs.
                                  VOICESPLIT_HEAD_BWD_GEMM */
   VS_OPT_ABLATION = 4,        /* libraries built with `make ABLATION=1` only (tools/wgrad_ablation.py, tools/split_conv_micro.py, tools/gemm_micro.py,
-                                 tools/conv_bench wgrad): selects a TIMING-ABLATION instance of the weight-gradient / split-f16 conv / bf16 GEMM
-                                 kernels (results are meaningless); the NCHW split-f16 weight gradient looks at it only while
-                                 vs_set_wgrad_kernel(3) pins its four-wave kernel.  Ignored by the product build, except that this pinned kernel
-                                 refuses to launch with a value other than 0 (the instances are not in the library).  VOICESPLIT_ABLATION */
+                                 tools/conv_bench): selects a TIMING-ABLATION instance of the weight-gradient / split-f16 conv / bf16 GEMM
+                                 kernels (results are meaningless); the NCHW split-f16 kernels look at it only while pinned: the weight
+                                 gradient under vs_set_wgrad_kernel(3) (its four-wave kernel), the 5x5 forward / data gradient under
+                                 vs_set_conv_kernel(2) (its persistent kernel).  Ignored by the product build, except that these pinned kernels
+                                 refuse to launch with a value other than 0 (the instances are not in the library).  VOICESPLIT_ABLATION */
   VS_OPT_DETERMINISTIC = 5,   /* VS_MATH_BF16 training step (vs_forward_train, vs_backward, vs_sisnr_loss): 1 = every partial sum that workgroups
                                  add to shared slots with fp64 atomics (BatchNorm statistics, their backward sums, cnn1's input moments,
                                  the loss head's moments) is added in WORKGROUP ORDER (the workgroups of such a launch that add to the same

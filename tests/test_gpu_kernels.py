@@ -122,6 +122,68 @@ def test_f16x3_dynamic_range():
     assert torch.equal(z, torch.zeros_like(z))
 
 
+CONV_KERNEL_CASES = [
+    # KT, KF, B, T, F, dil, act, data gradient too, modes
+    (5, 5, 2, 19, 37, 1, "mish", True, (0, 1, 2)),     # two full 8-row tiles + a 3-row tail launch; ragged F tile
+    (5, 5, 1, 20, 5, 1, "none", True, (0, 1, 2)),      # 4-row tail; F below one tile
+    (5, 5, 1, 21, 33, 1, "relu", False, (0, 1, 2)),    # 5 rows past 16: no tail launch, a third 8-row tile
+    (5, 5, 2, 40, 31, 16, "mish", False, (0, 1, 2)),   # residue classes of 3 and 2 rows: no full tile, the one-tile path picks 4-row tiles
+    (5, 5, 1, 70, 64, 2, "mish", False, (0, 1, 2)),    # 35 rows per class: four 8-row tiles + a 3-row tail; exact F tiles
+    (7, 1, 1, 8, 37, 1, "none", False, (0, 1)),        # 7x1 has the one-tile kernel only
+]
+
+
+def test_set_conv_kernel_modes_agree_bitwise():
+    """vs_set_conv_kernel: 0 = default, 1 = one tile per workgroup, 2 = persistent pipeline (5x5).  The two kernels contract in the
+    same K order with fp32 accumulation, so every mode must give the same bits, forward and data gradient, on every branch of the
+    dispatch (body + tail launch, no tail, 4-row tiles); mode 0's result is held to the fp64 reference at this file's tolerance.
+    Anything else (the former 100 + ablation modes included) is refused with -1 and leaves the mode where it was: the layer still
+    runs and gives the pinned mode's bits (the mode has no getter, and the bits are every mode's)."""
+    from voicesplit_amd import _lib, ops
+    lib = _lib.load()
+    d = dev()
+    try:
+        for KT, KF, B, T, Fq, dil, act, dgrad, modes in CONV_KERNEL_CASES:
+            g = torch.Generator().manual_seed(KT * 100 + dil * 10 + T)
+            x = torch.randn(B, 64, T, Fq, generator=g)
+            w = torch.randn(64, 64, KT, KF, generator=g) * (1.0 / (64 * KT * KF) ** 0.5)
+            b = torch.randn(64, generator=g) * 0.1
+            gamma, beta, mean, var = _bn(64, g)
+            scale, shift = ops.bn_fold(gamma.to(d), beta.to(d), mean.to(d), var.to(d), b.to(d))
+            xd, wd = x.to(d), w.to(d)
+            fwd, dx = {}, {}
+            for mode in modes:
+                assert lib.vs_set_conv_kernel(mode) == 0
+                fwd[mode] = ops.conv64(xd, wd, scale, shift, dil, act, math="f16x3")
+                if dgrad:
+                    dx[mode] = ops.conv64_dgrad(xd, wd, dil, math="f16x3")
+            case = (KT, KF, B, T, Fq, dil, act)
+            for mode in modes[1:]:
+                assert torch.equal(fwd[mode], fwd[0]), (case, mode)
+                assert not dgrad or torch.equal(dx[mode], dx[0]), (case, mode)
+            pt, pf = dil * (KT // 2), KF // 2
+            y = F.conv2d(F.pad(x.double(), (pf, pf, pt, pt)), w.double(), b.double(), dilation=(dil, 1))
+            y = (y - mean.double()[None, :, None, None]) / torch.sqrt(var.double()[None, :, None, None] + 1e-5)
+            y = y * gamma.double()[None, :, None, None] + beta.double()[None, :, None, None]
+            assert rel_err(fwd[0], y if act == "none" else R.activation(y, act)) < TOL, case
+            if dgrad:       # dIn = conv^T(dz, w): the same conv with the weights transposed and tap-flipped
+                wt = w.double().transpose(0, 1).flip(2, 3)
+                assert rel_err(dx[0], F.conv2d(F.pad(x.double(), (pf, pf, pt, pt)), wt, dilation=(dil, 1))) < TOL, case
+        # refusals, under the pinned one-tile kernel, on the first case's operands (x, w, ... of the loop's last case are 7x1)
+        KT, KF, B, T, Fq, dil, act = CONV_KERNEL_CASES[0][:7]
+        g = torch.Generator().manual_seed(5)
+        xd = torch.randn(B, 64, T, Fq, generator=g).to(d)
+        wd = (torch.randn(64, 64, KT, KF, generator=g) * 0.025).to(d)
+        ones, zeros = torch.ones(64, device=d), torch.zeros(64, device=d)
+        assert lib.vs_set_conv_kernel(1) == 0
+        pinned = ops.conv64(xd, wd, ones, zeros, dil, act, math="f16x3")
+        for bad in (-1, 3, 100, 101):
+            assert lib.vs_set_conv_kernel(bad) == -1, bad
+            assert torch.equal(ops.conv64(xd, wd, ones, zeros, dil, act, math="f16x3"), pinned), bad
+    finally:
+        assert lib.vs_set_conv_kernel(0) == 0
+
+
 @pytest.mark.parametrize("act", ["mish", "relu"])
 def test_conv_last_writes_lstm_feature_layout(act):
     from voicesplit_amd import ops

@@ -29,22 +29,12 @@
 //    from L2, as in the fp32 kernel, would need 42 B/clk/CU at this MFMA rate: first version,
 //    7.0 ms per layer against a 2.9 ms matrix-pipe floor.)
 //  * Epilogue: y = act(acc * (1/(s_in*s_w)) * scale[co] + shift[co]).
+#include "conv_f16x3_common.h"
 #include "vs_internal.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kCo = 64;
-constexpr int kCi = 64;
-constexpr int kChunk = 16;              // input channels per LDS stage = K of one MFMA
-constexpr int kNChunk = kCi / kChunk;   // 4
-constexpr unsigned kOob = 0x7FFFFFF0u;
-constexpr int kTileF = 32;
 constexpr int kPadTaps = 2;             // dummy (zero) tap blocks behind the packed weights
-constexpr int kTapBytes = 2 * 2 * 64 * 16;   // one (chunk, tap): 2 co blocks x 2 parts x 64 lanes x 16 B
 
 // ---- per-tensor power-of-two scale --------------------------------------------------------------
 // absmax over a tensor as an atomicMax on the bit pattern (non-negative floats order like uints)
@@ -85,16 +75,10 @@ __global__ void scale_from_absmax_kernel(const unsigned* __restrict__ amax, int 
   scale[1] = inv;
 }
 
-__device__ __forceinline__ void split2(float x0, float x1, f16x2& hi, f16x2& lo) {
-  hi = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-  lo = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0 - (float)hi[0], x1 - (float)hi[1]));
-}
-
-// packed weight layout: [chunk][tap][cb(2)][part(2)][lane(64)][8 x f16]; element j of the lane vector:
-//   part(W[co = cb*32 + (lane&31)][ci = chunk*16 + 8*(lane>>5) + j][kt][kf] * s_w)
+// w -> the packed weight layout of conv_f16x3_common.h
 // transpose_flip = 1: the data-gradient weights W'[co'][ci'][kt][kf] = W[ci'][co'][KT-1-kt][KF-1-kf]
 __global__ void conv_pack_weights_f16_kernel(const float* __restrict__ w, _Float16* __restrict__ wp, int KT, int KF,
-                                             int transpose_flip, const float* __restrict__ wscale, int bf16) {
+                                             int transpose_flip, const float* __restrict__ wscale) {
   const int NT = KT * KF;
   const int total = kNChunk * NT * 2 * 2 * 64 * 8;
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -111,17 +95,12 @@ __global__ void conv_pack_weights_f16_kernel(const float* __restrict__ w, _Float
   const int ci = chunk * kChunk + 8 * (lane >> 5) + j;
   const float v = (transpose_flip ? w[((ci * kCi + co) * KT + (KT - 1 - kt)) * KF + (KF - 1 - kf)]
                                   : w[((co * kCi + ci) * KT + kt) * KF + kf]) * wscale[0];
-  if (bf16) {      // VS_MATH_BF16: the hi slot carries the bf16 rounding of the weight, the lo slot is unused
-    const unsigned short b = (unsigned short)(vs_pack_bf16(v, 0.f) & 0xffffu);
-    wp[idx] = part ? (_Float16)0.f : __builtin_bit_cast(_Float16, b);
-    return;
-  }
   f16x2 hi, lo;
   split2(v, 0.f, hi, lo);
   wp[idx] = part ? lo[0] : hi[0];
 }
 
-template <int KT, int KF, int P, int ACT, int NTERM = 3, bool STATS = false>
+template <int KT, int KF, int P, int ACT, bool STATS = false>
 __global__ __launch_bounds__(256, 2)
 void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restrict__ wp,
                          const float* __restrict__ scale, const float* __restrict__ shift,
@@ -137,7 +116,6 @@ void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restric
   constexpr int NT = KT * KF;
   constexpr int GT = KF == 1 ? KT : KF;          // taps per weight group (one kt row; all taps for 7x1)
   constexpr int NGRP = NT / GT;                  // weight groups per ci chunk
-  constexpr int kTapVec = kTapBytes / 16;        // 256 x 16 B per tap
   // activations [pixel][4 slots][8 x f16] = 64 B per pixel (+ overrun rows for the one-tap-ahead
   // prefetch); weights: two buffers of GT taps in fragment order
   __shared__ __attribute__((aligned(16))) u32x4 sIn[(NPIX + (P + 1) * PX) * 4];
@@ -196,13 +174,6 @@ void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restric
         const int sw = ((pix % PX) >> 2) & 3;     // swizzle by window column (a row is 9*64 banks: no effect)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {        // ci 8h..8h+7
-          if (NTERM == 1) {                  // VS_MATH_BF16: one bf16 rounding per element, no lo half
-            u32x4 vb;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) vb[q] = vs_pack_bf16(stage[i][8 * h + 2 * q] * s_in, stage[i][8 * h + 2 * q + 1] * s_in);
-            sIn[pix * 4 + ((0 + h) ^ sw)] = vb;
-            continue;
-          }
           f16x2 hi[4], lo[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) split2(stage[i][8 * h + 2 * q] * s_in, stage[i][8 * h + 2 * q + 1] * s_in, hi[q], lo[q]);
@@ -248,7 +219,7 @@ void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restric
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-      for (int part = 0; part < (NTERM == 1 ? 1 : 2); ++part) a[cb][part] = sW[buf][g * kTapVec + (cb * 2 + part) * 64 + lane];
+      for (int part = 0; part < 2; ++part) a[cb][part] = sW[buf][g * kTapVec + (cb * 2 + part) * 64 + lane];
   };
   // B fragments of one tap: [row p][part]; pixel = (wave*P + p + kt)*PX + l31 + kf.  The lane-
   // dependent part of the (swizzled) address is precomputed per (kf, part); the row part is a
@@ -265,7 +236,7 @@ void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restric
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       bf[p][0] = bbase[kf][0][(p + kt) * PX * 4];
-      if (NTERM != 1) bf[p][1] = bbase[kf][1][(p + kt) * PX * 4];
+      bf[p][1] = bbase[kf][1][(p + kt) * PX * 4];
     }
   };
 
@@ -296,14 +267,6 @@ void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restric
           __builtin_amdgcn_sched_barrier(0);
           // product term outermost: consecutive MFMAs go to 2*P different accumulators, so no
           // MFMA waits on the result of the one issued just before it
-          if (NTERM == 1) {
-#pragma unroll
-            for (int p = 0; p < P; ++p)
-#pragma unroll
-              for (int cb = 0; cb < 2; ++cb)
-                acc[cb][p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(vs_bf16x8, a_cur[cb][0]),
-                                                                    __builtin_bit_cast(vs_bf16x8, b_cur[p][0]), acc[cb][p], 0, 0, 0);
-          } else {
 #pragma unroll
           for (int term = 0; term < 3; ++term) {
 #pragma unroll
@@ -315,7 +278,6 @@ void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restric
                 acc[cb][p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq, bq, acc[cb][p], 0, 0, 0);
               }
             }
-          }
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -391,7 +353,7 @@ void conv64_f16x3_kernel(const float* __restrict__ in, const _Float16* __restric
 template <int KT, int KF, int P>
 int launch_conv(const float* in, const _Float16* wp, const float* scale, const float* shift, const float* in_scale,
                 const float* w_scale, float* out, int B, int T, int F, int dil, int act, unsigned* amax_out, hipStream_t stream,
-                int i_base = 0, int i_end = 0x7fffffff, int math = VS_MATH_CODE_F16X3, double* bn_stats = nullptr) {
+                int i_base = 0, int i_end = 0x7fffffff, double* bn_stats = nullptr) {
   constexpr int R = 4 * P;
   const int rows_all = (T + dil - 1) / dil;
   const int rows_max = (rows_all < i_end ? rows_all : i_end) - i_base;
@@ -400,28 +362,15 @@ int launch_conv(const float* in, const _Float16* wp, const float* scale, const f
   const long long nblk = (long long)B * dil * n_rt * n_ft;
   VS_REQUIRE(nblk > 0 && nblk < 2147483647LL, "conv64_f16x3: grid of %lld blocks out of range", nblk);
   dim3 grid((unsigned)nblk), block(256);
+  auto launch = [&](auto A, auto S) {
+    hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, decltype(A)::value, decltype(S)::value>), grid, block, 0, stream, in, wp, scale, shift,
+                       in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, bn_stats);
+  };
   if (bn_stats) {        // train-mode forward: conv + bias, statistics fused into the epilogue
     VS_REQUIRE(act == VS_ACT_NONE, "conv64_f16x3: fused BatchNorm statistics need act = NONE");
-    if (math == VS_MATH_CODE_BF16) hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_NONE, 1, true>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, bn_stats);
-    else hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_NONE, 3, true>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, bn_stats);
-    VS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (math == VS_MATH_CODE_BF16) {
-    switch (act) {
-      case VS_ACT_RELU: hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_RELU, 1>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, (double*)nullptr); break;
-      case VS_ACT_MISH: hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_MISH, 1>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, (double*)nullptr); break;
-      case VS_ACT_NONE: hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_NONE, 1>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, (double*)nullptr); break;
-      default: VS_REQUIRE(false, "conv64_f16x3: unknown activation %d", act);
-    }
-    VS_LAUNCH_CHECK();
-    return 0;
-  }
-  switch (act) {
-    case VS_ACT_RELU: hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_RELU>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, (double*)nullptr); break;
-    case VS_ACT_MISH: hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_MISH>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, (double*)nullptr); break;
-    case VS_ACT_NONE: hipLaunchKernelGGL((conv64_f16x3_kernel<KT, KF, P, VS_ACT_NONE>), grid, block, 0, stream, in, wp, scale, shift, in_scale, w_scale, out, T, F, dil, n_rt, n_ft, amax_out, i_base, i_end, (double*)nullptr); break;
-    default: VS_REQUIRE(false, "conv64_f16x3: unknown activation %d", act);
+    launch(std::integral_constant<int, VS_ACT_NONE>(), std::true_type());
+  } else if (int rc = conv_f16x3_dispatch_act(act, "conv64_f16x3", [&](auto A) { launch(A, std::false_type()); })) {
+    return rc;
   }
   VS_LAUNCH_CHECK();
   return 0;
@@ -471,60 +420,57 @@ int vs_pow2_scale_impl(const float* x, long long n, unsigned* amax_scratch, floa
 
 // w [64][64][KT][KF] fp32 -> fragment-ordered hi/lo f16 (scaled by w_scale2[0], which this call computes)
 int vs_conv64_pack_f16_impl(const float* w, _Float16* wp, int KT, int KF, int transpose_flip, unsigned* amax_scratch,
-                            float* w_scale2, hipStream_t stream, int math) {
+                            float* w_scale2, hipStream_t stream) {
   VS_REQUIRE((KT == 7 && KF == 1) || (KT == 5 && KF == 5), "conv64_f16x3: unsupported kernel %dx%d", KT, KF);
   if (int rc = vs_pow2_scale_impl(w, (long long)kCo * kCi * KT * KF, amax_scratch, w_scale2, stream)) return rc;
   const int total = (int)(vs_conv64_packed_f16_floats(KT, KF) * 2);
-  hipLaunchKernelGGL(conv_pack_weights_f16_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, w, wp, KT, KF, transpose_flip, w_scale2,
-                     math == VS_MATH_CODE_BF16 ? 1 : 0);
+  hipLaunchKernelGGL(conv_pack_weights_f16_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, w, wp, KT, KF, transpose_flip, w_scale2);
   VS_LAUNCH_CHECK();
   return 0;
 }
 
 // which 5x5 kernel vs_conv64_f16x3_fwd_impl launches: 0 = default (persistent pipeline), 1 = one tile per
 // workgroup (this file), 2 = persistent pipeline (conv_f16x3_pk.hip).  Test / A-B switch, process-global.
+// Anything else is refused and leaves the mode alone.  (The timing ablations of the persistent kernel are
+// instances of ABLATION=1 libraries, selected by mode 2 + VS_OPT_ABLATION.)
 static int g_conv_kernel = 0;
 extern "C" int vs_set_conv_kernel(int mode) {
-  VS_REQUIRE((mode >= 0 && mode <= 2) || (mode >= 100 && mode <= 130), "vs_set_conv_kernel: mode %d", mode);   // 100+abl: timing ablations
+  if (mode < 0 || mode > 2) return -1;
   g_conv_kernel = mode;
   return 0;
 }
 
 int vs_conv64_f16x3_fwd_impl(const float* in, const _Float16* wp, const float* scale, const float* shift,
                              const float* in_scale2, const float* w_scale2, float* out,
-                             int B, int T, int F, int KT, int KF, int dil, int act, unsigned* amax_out, hipStream_t stream, int math,
+                             int B, int T, int F, int KT, int KF, int dil, int act, unsigned* amax_out, hipStream_t stream,
                              double* bn_stats) {
   VS_REQUIRE(B > 0 && T > 0 && F > 0 && dil > 0, "conv64_f16x3: bad shape B=%d T=%d F=%d dil=%d", B, T, F, dil);
   VS_REQUIRE((long long)kChunk * T * F * 4 < (long long)kOob, "conv64_f16x3: T*F=%lld too large for 32-bit slab offsets", (long long)T * F);
-  if (KT == 5 && KF == 5 && g_conv_kernel != 1 && (long long)kCo * T * F * 4 < (long long)kOob) {
-    // persistent pipelined kernel on 8-row tiles; when the residue classes end 1..4 rows past a multiple
-    // of 8 (dil = 16 at T = 301: 19 rows) the 4-row one-tile kernel takes that tail, as in the legacy path
-    const int rows_all = (T + dil - 1) / dil, full8 = rows_all / 8 * 8, rem = rows_all - full8;
-    const bool tail = full8 > 0 && rem > 0 && rem <= 4;
-    if (int rc = vs_conv64_f16x3_pk_impl(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream,
-                                         g_conv_kernel >= 100 ? g_conv_kernel - 100 : 0, tail ? full8 : 0x7fffffff, math, bn_stats)) return rc;
-    return tail ? launch_conv<5, 5, 1>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, full8, 0x7fffffff, math, bn_stats) : 0;
-  }
+  VS_REQUIRE((KT == 7 && KF == 1) || (KT == 5 && KF == 5), "conv64_f16x3: unsupported kernel %dx%d", KT, KF);
   // 8-row tiles (P = 2) amortise the KT-1 halo rows and the weight staging over twice the MFMAs
   // (measured 6.6 vs 7.45 ms per layer at equal padding); 4-row tiles only win when they avoid
   // more than ~12 % of padded rows (short residue classes: dil = 16 at T = 301).
   const bool p2 = tile_rows(T, dil, 8) * 100 <= tile_rows(T, dil, 4) * 112;
-  // Mixed tiling: when the residue classes end 1..4 rows past a multiple of 8 (dil = 16 at T = 301:
-  // 19 rows), the 8-row kernel takes the full tiles and the 4-row kernel the tail, instead of
-  // running everything on the less efficient 4-row tiles or padding a third 8-row tile.
+  const int all = 0x7fffffff;
+  // the one-tile kernel with 4*P_-row tiles on rows [I0_, I1_) of every residue class
+#define VS_ONE_TILE(KT_, KF_, P_, I0_, I1_) \
+  launch_conv<KT_, KF_, P_>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, I0_, I1_, bn_stats)
+  if (KT == 7) return p2 ? VS_ONE_TILE(7, 1, 2, 0, all) : VS_ONE_TILE(7, 1, 1, 0, all);
+  // 5x5.  Mixed tiling: when the residue classes end 1..4 rows past a multiple of 8 (dil = 16 at T = 301: 19 rows), the
+  // body takes the full 8-row tiles and the 4-row one-tile kernel the tail, instead of running everything on the less
+  // efficient 4-row tiles or padding a third 8-row tile.
   const int rows_all = (T + dil - 1) / dil, full8 = rows_all / 8 * 8, rem = rows_all - full8;
-  if (KT == 5 && KF == 5 && full8 > 0 && rem > 0 && rem <= 4) {
-    if (int rc = launch_conv<5, 5, 2>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, 0, full8, math, bn_stats)) return rc;
-    return launch_conv<5, 5, 1>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, full8, 0x7fffffff, math, bn_stats);
+  const bool tail = full8 > 0 && rem > 0 && rem <= 4;
+  const int body_end = tail ? full8 : all;
+  int rc;
+  if (g_conv_kernel != 1 && (long long)kCo * T * F * 4 < (long long)kOob) {      // persistent pipelined kernel, 8-row tiles
+    // its timing ablations (tools/conv_bench): pinned (mode 2) + VS_OPT_ABLATION, instances of ABLATION=1 libraries
+    rc = vs_conv64_f16x3_pk_impl(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream,
+                                 g_conv_kernel == 2 ? vs_opt(VS_OPT_ABLATION) : 0, body_end, bn_stats);
+  } else {
+    rc = tail || p2 ? VS_ONE_TILE(5, 5, 2, 0, body_end) : VS_ONE_TILE(5, 5, 1, 0, body_end);
   }
-  if (KT == 7 && KF == 1) {
-    return p2 ? launch_conv<7, 1, 2>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, 0, 0x7fffffff, math, bn_stats)
-              : launch_conv<7, 1, 1>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, 0, 0x7fffffff, math, bn_stats);
-  }
-  if (KT == 5 && KF == 5) {
-    return p2 ? launch_conv<5, 5, 2>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, 0, 0x7fffffff, math, bn_stats)
-              : launch_conv<5, 5, 1>(in, wp, scale, shift, in_scale2, w_scale2, out, B, T, F, dil, act, amax_out, stream, 0, 0x7fffffff, math, bn_stats);
-  }
-  VS_REQUIRE(false, "conv64_f16x3: unsupported kernel %dx%d", KT, KF);
-  return -1;
+  if (rc || !tail) return rc;
+  return VS_ONE_TILE(5, 5, 1, full8, all);
+#undef VS_ONE_TILE
 }

@@ -1,6 +1,6 @@
 // Persistent, software-pipelined form of the 5x5 64->64 split-f16 convolution (conv_f16x3.hip has
-// the arithmetic, the packed-weight layout and the one-tile-per-workgroup kernel this one replaces
-// for cnn3..cnn7 forward + data gradient: models/voicesplit/model.py:26-48).
+// the arithmetic and the one-tile-per-workgroup kernel this one replaces for cnn3..cnn7 forward + data
+// gradient: models/voicesplit/model.py:26-48; conv_f16x3_common.h has the packed-weight layout).
 //
 // What rocprofv3 showed for the one-tile kernel (profiles/r01_train_rocprof): matrix pipe 60 % busy,
 // waves parked 25 % of their cycles -- not on memory (every s_waitcnt in front of its barriers is
@@ -23,24 +23,13 @@
 //    group body is branch-free straight-line code (non-existent next steps / out-of-tile stores are
 //    predicated through the buffer descriptor's range check), and a wave's instruction stream is
 //    MFMA-dense: 12 MFMAs + 8 ds_read_b128 + <= ~35 staging/epilogue instructions per tap.
-// Results are bit-identical to conv64_f16x3_kernel (same K order, same fp32 accumulation).
-#include "vs_common.h"
+// Results are bit-identical to conv64_f16x3_kernel (same K order, same fp32 accumulation):
+// tests/test_gpu_kernels.py test_set_conv_kernel_modes_agree_bitwise, tools/conv_bench.
+#include "conv_f16x3_common.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kCo = 64;
-constexpr int kCi = 64;
-constexpr int kChunk = 16;
-constexpr int kNChunk = 4;
-constexpr unsigned kOob = 0x7FFFFFF0u;
-constexpr int kTileF = 32;
 constexpr int KT = 5, KF = 5;
-constexpr int kTapBytes = 2 * 2 * 64 * 16;     // one (chunk, tap): 2 co blocks x 2 parts x 64 lanes x 16 B
-constexpr int kTapVec = kTapBytes / 16;        // 256
 constexpr int kGroupVec = KF * kTapVec;        // one kt row of taps: 1280 x 16 B = 20 KB
 constexpr int kNGroups = kNChunk * KT;         // 20 weight groups per tile
 
@@ -63,11 +52,6 @@ struct Tile {
   int b, cls, i0, f0, n_all, n_c;
   bool valid;
 };
-
-__device__ __forceinline__ void split2(float x0, float x1, f16x2& hi, f16x2& lo) {
-  hi = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-  lo = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0 - (float)hi[0], x1 - (float)hi[1]));
-}
 
 // Workgroup rendezvous that orders LDS traffic only: the pending ds_writes of this wave are retired
 // (lgkmcnt) and nothing else is waited for -- global loads issued for later steps and the epilogue's
@@ -139,9 +123,7 @@ __device__ __forceinline__ Tile seek_tile(TileWalk& w, const PkArgs& a) {
 // STATS: the epilogue also accumulates the per-channel sum and sum of squares of what it stores (train-mode
 // BatchNorm statistics of the layer, SURVEY.md 7 hard-part 3): per-lane fp32 partial sums over all tiles of the
 // workgroup, combined across lanes / waves once at the end, one fp64 atomicAdd per channel and workgroup.
-// NT: product terms per fp32 product: 3 = split f16 (hi*hi + hi*lo + lo*hi), 1 = single-pass bf16 (VS_MATH_BF16:
-// operands rounded to bf16, the lo slots of the LDS images stay unused).
-template <int P, int ACT, int ABL = 0, int FILL = 0, int NT = 3, bool STATS = false>
+template <int P, int ACT, int ABL = 0, int FILL = 0, bool STATS = false>
 __global__ __launch_bounds__(256, 1)
 void conv64_f16x3_pk_kernel(PkArgs a) {
   constexpr int R = 4 * P;
@@ -216,12 +198,6 @@ void conv64_f16x3_pk_kernel(PkArgs a) {
     u32x4* dst = win + (pdst[i] & 0x0fffffff);
     asm volatile("" : "+v"(stage[i][8 * h]));     // pins the unit's conversion to the tap it was placed in
     u32x4 vh, vl;
-    if (NT == 1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) vh[q] = vs_pack_bf16(stage[i][8 * h + 2 * q] * s_in, stage[i][8 * h + 2 * q + 1] * s_in);
-      dst[(0 + h) ^ sw] = vh;
-      return;
-    }
     f16x2 hi[4], lo[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) split2(stage[i][8 * h + 2 * q] * s_in, stage[i][8 * h + 2 * q + 1] * s_in, hi[q], lo[q]);
@@ -314,13 +290,13 @@ void conv64_f16x3_pk_kernel(PkArgs a) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-      for (int part = 0; part < (NT == 1 ? 1 : 2); ++part) af[cb][part] = wb[g * kTapVec + (cb * 2 + part) * 64 + lane];
+      for (int part = 0; part < 2; ++part) af[cb][part] = wb[g * kTapVec + (cb * 2 + part) * 64 + lane];
   };
   auto load_b = [&](const u32x4* wn, int kt, int kf, u32x4 (&bf)[P][2]) {
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       bf[p][0] = wn[boff[kf][0] + (p + kt) * PX * 4];
-      if (NT != 1) bf[p][1] = wn[boff[kf][1] + (p + kt) * PX * 4];
+      bf[p][1] = wn[boff[kf][1] + (p + kt) * PX * 4];
     }
   };
 
@@ -416,14 +392,6 @@ void conv64_f16x3_pk_kernel(PkArgs a) {
           // (3) the weights fetched at the head of this group go to the ring
           if (g == 3 && !(ABL & 2)) store_w(wbuf2);
           // --- the tap: term outermost so consecutive MFMAs hit different accumulators ---------------
-          if (NT == 1) {
-#pragma unroll
-            for (int p = 0; p < P; ++p)
-#pragma unroll
-              for (int cb = 0; cb < 2; ++cb)
-                acc[cb * P + p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(vs_bf16x8, a_cur[cb][0]),
-                                                                         __builtin_bit_cast(vs_bf16x8, b_cur[p][0]), acc[cb * P + p], 0, 0, 0);
-          } else {
 #pragma unroll
           for (int term = 0; term < 3; ++term) {
 #pragma unroll
@@ -436,12 +404,11 @@ void conv64_f16x3_pk_kernel(PkArgs a) {
               }
             }
           }
-          }
           // issue pattern of the tap: one MFMA, then up to FILL instructions of any other kind -- the
           // matrix pipe is busy 32 cycles per MFMA, which covers ~7 issue slots of this (only) wave
           if (FILL > 0) {
 #pragma unroll
-            for (int m = 0; m < NT * 2 * P; ++m) {
+            for (int m = 0; m < 3 * 2 * P; ++m) {
               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
               __builtin_amdgcn_sched_group_barrier(0x6f6, FILL, 0);   // VALU | SALU | VMEM | DS | TRANS
             }
@@ -532,7 +499,7 @@ void conv64_f16x3_pk_kernel(PkArgs a) {
 }
 
 template <int P>
-int launch_pk(const PkArgs& a0, int act, int i_base, int i_end, hipStream_t stream, int abl = 0, int math = VS_MATH_CODE_F16X3) {
+int launch_pk(const PkArgs& a0, int act, int i_base, int i_end, hipStream_t stream, int abl = 0) {
   constexpr int R = 4 * P;
   PkArgs a = a0;
   a.i_base = i_base;
@@ -554,7 +521,7 @@ int launch_pk(const PkArgs& a0, int act, int i_base, int i_end, hipStream_t stre
   if (nwg > (a.n_tiles + 7) / 8 * 8) nwg = (a.n_tiles + 7) / 8 * 8;
   dim3 grid((unsigned)nwg), block(256);
 #ifdef VS_ABLATION        // timing ablations of the kernel (tools/conv_bench): make -C voicesplit_amd/csrc ABLATION=1
-  if (abl) {      // timing ablations (Mish epilogue), see the kernel's ABL parameter
+  if (abl) {      // vs_set_conv_kernel(2) + VS_OPT_ABLATION; Mish epilogue, see the kernel's ABL (1..15) and FILL (20 + FILL) parameters
     switch (abl) {
       case 1: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_MISH, 1>), grid, block, 0, stream, a); break;
       case 2: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_MISH, 2>), grid, block, 0, stream, a); break;
@@ -578,26 +545,11 @@ int launch_pk(const PkArgs& a0, int act, int i_base, int i_end, hipStream_t stre
 #endif
   if (a.bn_stats) {      // train-mode forward: conv + bias, no activation, statistics fused
     VS_REQUIRE(act == VS_ACT_NONE, "conv64_f16x3_pk: fused BatchNorm statistics need act = NONE");
-    if (math == VS_MATH_CODE_BF16) hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_NONE, 0, 0, 1, true>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_NONE, 0, 0, 3, true>), grid, block, 0, stream, a);
-    VS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (math == VS_MATH_CODE_BF16) {
-    switch (act) {
-      case VS_ACT_RELU: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_RELU, 0, 0, 1>), grid, block, 0, stream, a); break;
-      case VS_ACT_MISH: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_MISH, 0, 0, 1>), grid, block, 0, stream, a); break;
-      case VS_ACT_NONE: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_NONE, 0, 0, 1>), grid, block, 0, stream, a); break;
-      default: VS_REQUIRE(false, "conv64_f16x3_pk: unknown activation %d", act);
-    }
-    VS_LAUNCH_CHECK();
-    return 0;
-  }
-  switch (act) {
-    case VS_ACT_RELU: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_RELU>), grid, block, 0, stream, a); break;
-    case VS_ACT_MISH: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_MISH>), grid, block, 0, stream, a); break;
-    case VS_ACT_NONE: hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_NONE>), grid, block, 0, stream, a); break;
-    default: VS_REQUIRE(false, "conv64_f16x3_pk: unknown activation %d", act);
+    hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, VS_ACT_NONE, 0, 0, true>), grid, block, 0, stream, a);
+  } else if (int rc = conv_f16x3_dispatch_act(act, "conv64_f16x3_pk", [&](auto A) {
+               hipLaunchKernelGGL((conv64_f16x3_pk_kernel<P, decltype(A)::value>), grid, block, 0, stream, a);
+             })) {
+    return rc;
   }
   VS_LAUNCH_CHECK();
   return 0;
@@ -609,9 +561,9 @@ int launch_pk(const PkArgs& a0, int act, int i_base, int i_end, hipStream_t stre
 int vs_conv64_f16x3_pk_impl(const float* in, const _Float16* wp, const float* scale, const float* shift,
                             const float* in_scale2, const float* w_scale2, float* out,
                             int B, int T, int F, int dil, int act, unsigned* amax_out, hipStream_t stream, int abl,
-                            int i_end, int math, double* bn_stats) {
+                            int i_end, double* bn_stats) {
   VS_REQUIRE(B > 0 && T > 0 && F > 0 && dil > 0, "conv64_f16x3_pk: bad shape B=%d T=%d F=%d dil=%d", B, T, F, dil);
   VS_REQUIRE((long long)kCo * T * F * 4 < (long long)kOob, "conv64_f16x3_pk: T*F=%lld too large for 32-bit offsets", (long long)T * F);
   PkArgs a{in, wp, scale, shift, in_scale2, w_scale2, out, amax_out, bn_stats, B, T, F, dil, 0, 0, 0, 0, 0, 0, 0};
-  return launch_pk<2>(a, act, 0, i_end, stream, abl, math);
+  return launch_pk<2>(a, act, 0, i_end, stream, abl);
 }

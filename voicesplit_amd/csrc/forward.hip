@@ -169,16 +169,18 @@ int vs_check_dims_impl(const vs_dims* d) { return check_dims(d); }
 int vs_conv64_layer_impl(int math, const float* in, const float* w, void* packed, float* scales8 /* one scale slot */, int in_amax_ready,
                          const float* scale, const float* shift, float* out, int B, int T, int F, int KT, int KF,
                          int dil, int act, int transpose_flip, unsigned* amax_out, hipStream_t stream, double* bn_stats) {
-  if (math != VS_MATH_FP32) {      // split-f16 or single-pass bf16: same operand plumbing (power-of-two scales, packed images)
+  VS_REQUIRE(math == VS_MATH_FP32 || math == VS_MATH_F16X3,
+             "conv64 layer: math=%d has no NCHW kernels (the bf16 arithmetic is channels-last)", math);
+  if (math == VS_MATH_F16X3) {     // power-of-two operand scales, packed hi / lo weight image
     if (in_amax_ready) {
       if (int rc = vs_scale_from_absmax_impl(vs_amax_slot(scales8), VS_AMAX_SLOTS, scales8, stream)) return rc;
     } else {
       if (int rc = vs_pow2_scale_impl(in, (long long)B * 64 * T * F, vs_amax_slot(scales8), scales8, stream)) return rc;
     }
     if (int rc = vs_conv64_pack_f16_impl(w, static_cast<_Float16*>(packed), KT, KF, transpose_flip,
-                                         reinterpret_cast<unsigned*>(scales8 + 4), scales8 + 2, stream, math)) return rc;
+                                         reinterpret_cast<unsigned*>(scales8 + 4), scales8 + 2, stream)) return rc;
     return vs_conv64_f16x3_fwd_impl(in, static_cast<const _Float16*>(packed), scale, shift, scales8, scales8 + 2, out,
-                                    B, T, F, KT, KF, dil, act, amax_out, stream, math, bn_stats);
+                                    B, T, F, KT, KF, dil, act, amax_out, stream, bn_stats);
   }
   VS_REQUIRE(bn_stats == nullptr, "conv64 layer: fused BatchNorm statistics are not offered by the fp32 kernels");
   if (int rc = vs_conv64_pack_impl(w, static_cast<float*>(packed), KT, KF, transpose_flip, stream)) return rc;
@@ -433,7 +435,7 @@ int convs_nchw(const Fwd& f, const float* x, float* feat) {
   float* abuf[2] = {f.at<float>(f.L.act0), f.at<float>(f.L.act1)};
   double* stats = f.stats();
   float* cs = f.at<float>(f.L.conv_scales);
-  const bool split = f.d->math != VS_MATH_FP32;      // (train mode only: the eval forward of that arithmetic is channels-last)
+  const bool split = f.d->math == VS_MATH_F16X3;     // (train mode only: the eval forward of that arithmetic is channels-last)
   if (split) VS_CHECK_HIP(hipMemsetAsync(cs, 0, 8 * VS_SCALE_SLOT_FLOATS * sizeof(float), f.stream));
   auto amax_for = [&](int consumer_layer) -> unsigned* {    // consumer_layer = conv index 1..6 (cnn2..cnn7)
     return (split && consumer_layer >= 1 && consumer_layer <= 6) ? vs_amax_slot(cs + VS_SCALE_SLOT_FLOATS * consumer_layer) : nullptr;

@@ -269,7 +269,7 @@ int arm(const Step& st) {
   VS_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st.ones), 0x3f800000 /* 1.0f */, 64, st.stream));
   VS_CHECK_HIP(hipMemsetAsync(st.zeros, 0, 64 * sizeof(float), st.stream));
   // split-f16 convs: the BatchNorm+activation pass that produces a layer's input also folds its |max| into that layer's scale slot
-  if (st.d->math != VS_MATH_FP32) VS_CHECK_HIP(hipMemsetAsync(st.cs, 0, 16 * VS_SCALE_SLOT_FLOATS * sizeof(float), st.stream));
+  if (st.d->math == VS_MATH_F16X3) VS_CHECK_HIP(hipMemsetAsync(st.cs, 0, 16 * VS_SCALE_SLOT_FLOATS * sizeof(float), st.stream));
   return 0;
 }
 
@@ -369,7 +369,7 @@ int bn_fp32(const Step& st, int l, const float* z, float* a, int C, bool feat_la
   const vs_conv_layer& c = st.p->conv[l];
   const BnConsts k = st.bn(l);
   const int B = st.B, T = st.T, F = st.F;
-  unsigned* amax = (st.d->math != VS_MATH_FP32 && l + 1 <= 6) ? vs_amax_slot(st.cs + VS_SCALE_SLOT_FLOATS * (l + 1)) : nullptr;
+  unsigned* amax = (st.d->math == VS_MATH_F16X3 && l + 1 <= 6) ? vs_amax_slot(st.cs + VS_SCALE_SLOT_FLOATS * (l + 1)) : nullptr;
   if (st.train) {
     return feat_layout
                ? vs_bn_train_feat_impl(z, a, B, T, F, c.bn_weight, c.bn_bias, c.bn_running_mean, c.bn_running_var, kBnEps,
@@ -393,7 +393,7 @@ int convs_nchw(const Step& st, const float* x) {
   }
   if (int rc = bn_fp32(st, 0, st.at<float>(L.z[0]), st.at<float>(L.a[0]), 64, false)) return rc;
   // batch statistics of z accumulated by the conv epilogue itself (split-f16 kernels): one pass less over z
-  const bool fuse = st.train && st.d->math != VS_MATH_FP32;
+  const bool fuse = st.train && st.d->math == VS_MATH_F16X3;
   for (int i = 0; i < 6; ++i) {
     const int l = i + 1;
     {
@@ -667,7 +667,7 @@ int dfeat_and_leaves(const Step& st, SideJoin& sj, const float* dvec, const vs_g
 // cnn8's BatchNorm + activation backward on the fp32 features: dfeat -> dz8, in place
 int features_bn_bwd(const Step& st, const vs_grads* g) {
   // split-f16 convs: dz of layer l is the operand of its data- and weight-gradient launches; the
-  // BatchNorm backward pass that produces it folds its |max| into slot 8+l
+  // BatchNorm backward pass that produces it folds its |max| into slot 8+l  (this function serves the bf16 route too)
   if (st.d->math != VS_MATH_FP32) VS_CHECK_HIP(hipMemsetAsync(st.cs + 8 * VS_SCALE_SLOT_FLOATS, 0, 8 * VS_SCALE_SLOT_FLOATS * sizeof(float), st.stream));
   VsProfScope ps(VS_PROF_BWD_BN, st.stream);
   const BnConsts k = st.bn(7);
@@ -762,7 +762,7 @@ int convs_bwd_nchw(const Step& st, SideJoin& sj, const float* x, const vs_grads*
   const vs_tape_layout& L = st.L;
   hipStream_t stream = st.stream;
   const int B = st.B, T = st.T, F = st.F;
-  const bool f16x3 = st.d->math != VS_MATH_FP32;
+  const bool f16x3 = st.d->math == VS_MATH_F16X3;
   float* dfeat = st.at<float>(L.dfeat);
   float* gbuf[2] = {st.at<float>(L.grad0), st.at<float>(L.grad1)};
   int cur = 0;

@@ -88,18 +88,20 @@ int vs_lstm_input_gemm_impl(int math, const float* feat, int K, const float* w_i
                             void* scratch, size_t scratch_bytes, hipStream_t, const VsLstmGemmReady& ready = VsLstmGemmReady());
 int vs_lstm_split_wih_impl(int math, const float* w_ih0, const float* w_ih1, int H, int K, int KE, unsigned* amax1,
                            float* w_scale2, _Float16* Wh, _Float16* Wl, hipStream_t);
+// conv_f16x3.hip: the NCHW 64->64 convs in the split-f16 arithmetic (VS_MATH_F16X3 only: the bf16 arithmetic is channels-last, conv_nhwc.hip)
 int vs_conv64_pack_f16_impl(const float* w, _Float16* wp, int KT, int KF, int transpose_flip, unsigned* amax_scratch,
-                            float* w_scale2, hipStream_t, int math = VS_MATH_CODE_F16X3);
+                            float* w_scale2, hipStream_t);
 int vs_conv64_f16x3_fwd_impl(const float* in, const _Float16* wp, const float* scale, const float* shift,
                              const float* in_scale2, const float* w_scale2, float* out,
                              int B, int T, int F, int KT, int KF, int dil, int act, unsigned* amax_out, hipStream_t,
-                             int math = VS_MATH_CODE_F16X3, double* bn_stats = nullptr);
+                             double* bn_stats = nullptr);
 // conv_f16x3_pk.hip: persistent, software-pipelined form of the 5x5 kernel (same contract, bit-identical results)
 int vs_conv64_f16x3_pk_impl(const float* in, const _Float16* wp, const float* scale, const float* shift,
                             const float* in_scale2, const float* w_scale2, float* out,
                             int B, int T, int F, int dil, int act, unsigned* amax_out, hipStream_t, int ablation = 0,
-                            int i_end = 0x7fffffff, int math = VS_MATH_CODE_F16X3, double* bn_stats = nullptr);
-// One 64->64 conv launch in either arithmetic: packs the weights (transpose_flip for the data
+                            int i_end = 0x7fffffff, double* bn_stats = nullptr);
+// One NCHW 64->64 conv launch in fp32 or split-f16 arithmetic (any other `math` is refused: the bf16
+// arithmetic is channels-last): packs the weights (transpose_flip for the data
 // gradient) into `packed`.  Split-f16 mode keeps its operand scales in one "scale slot" of
 // VS_SCALE_SLOT_FLOATS floats: [0..1] input {s, 1/s}, [2..3] weight {s, 1/s}, [4] uint |max| of
 // the weights, [8 .. 8+VS_AMAX_SLOTS) uint running |max| array of the input.
@@ -110,7 +112,7 @@ int vs_conv64_f16x3_pk_impl(const float* in, const _Float16* wp, const float* sc
 int vs_conv64_layer_impl(int math, const float* in, const float* w, void* packed, float* slot, int in_amax_ready,
                          const float* scale, const float* shift, float* out, int B, int T, int F, int KT, int KF,
                          int dil, int act, int transpose_flip, unsigned* amax_out, hipStream_t,
-                         double* bn_stats = nullptr);   // split-f16 / bf16 only: fused train-mode BatchNorm statistics of `out`
+                         double* bn_stats = nullptr);   // split-f16 only: fused train-mode BatchNorm statistics of `out`
 inline unsigned* vs_amax_slot(float* slot) { return reinterpret_cast<unsigned*>(slot + 8); }
 // conv_nhwc.hip: channels-last bf16 64->64 convs (VS_MATH_BF16)
 size_t vs_nhwc_packed_bytes(int KT, int KF);
