@@ -262,6 +262,28 @@ int vs_bilstm_fwd_carry(const vs_dims* dims, const vs_params* params, const floa
                         const float* state_in, float* state_out, int keep,
                         void* workspace, size_t workspace_bytes, float* lstm_out, void* stream);
 
+/* ---- the same for K enrolled speakers of one live mixture: one conv window and one input GEMM per chunk -------------
+ * feat [B][T][8F] (the chunk's features, computed once per mixture), dvecs [B][K][E] -> lstm_out [B][K][T][2H].  The two
+ * forms above composed: the input GEMM runs once per mixture WITHOUT row bias into G [B][T][8H], the row biases
+ * rb [B*K][8H] come from one small GEMM with M = B*K, and the tagged persistent recurrence runs the N = B*K sequences
+ * n = b*K + k in its carry x shared-input mode: column n reads row b of G, adds its own resident row bias in fp32 before the
+ * gate functions, starts its forward direction from state_in[n] and hands h and c behind frame keep - 1 to state_out[n]
+ * (state_in, state_out [B*K][2][H] fp32: h, then c; state_in = NULL: zero state).  Reverse direction, rows t >= keep and the
+ * meaning of keep as in vs_bilstm_fwd_carry.  Guarantees:
+ *   (a) two calls over [0, a) and [a, T), the second given the first's state_out, give the forward half of one call over
+ *       [0, T) bit for bit, per column;
+ *   (b) with state_in = NULL and keep = T, lstm_out is bit-identical to vs_bilstm_fwd_multi's (lengths = NULL);
+ *   (c) state_in and state_out may be the same buffer, as in vs_bilstm_fwd_carry;
+ *   (d) row [b][k] is what vs_bilstm_fwd_carry gives for feat[b], dvecs[b][k], state_in[b*K + k] -- not bit-identical: the
+ *       row bias is added by the recurrence, not by the GEMM's epilogue.
+ * Eval mode only; weights derived per call, as in every stage call.  Refused with an error code and a message, never computed
+ * some other way -- what vs_bilstm_fwd_carry and vs_bilstm_fwd_multi refuse: VS_MATH_FP32, H > 448, vs_set_lstm_kernel not 0
+ * or 2, a grid that is not resident, keep outside [1, T], NULL state_out, K < 1, NULL dvecs.  No per-item lengths: a stream has
+ * none.  workspace: vs_multi_workspace_bytes(dims, K).  The head is vs_head_fwd over dims with B := B*K. */
+int vs_bilstm_fwd_carry_multi(const vs_dims* dims, const vs_params* params, const float* feat, const float* dvecs, int K,
+                              const float* state_in, float* state_out, int keep,
+                              void* workspace, size_t workspace_bytes, float* lstm_out, void* stream);
+
 /* ---- kernels (unit-test surface) --------------------------------------------------------- */
 /* BN(conv+bias) = conv*scale + shift */
 int vs_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,
@@ -435,6 +457,12 @@ int vs_bilstm_recurrent_math(const float* xg, const float* packed_whh, float* st
  * everything else is refused as vs_bilstm_fwd_carry refuses it. */
 int vs_bilstm_recurrent_carry(const float* xg, const float* packed_whh, float* state, float* out, const float* state_in,
                               float* state_out, int keep, int B, int T, int H, int math, void* stream);
+/* The raw form of vs_bilstm_fwd_carry_multi: N = M*K sequences, sequence n = m*K + k reads row m of xg [M][T][8H] (the input GEMM
+ * WITHOUT row bias) and adds rowbias[n] of rowbias [N][8H]; state_in [N][2][H] or NULL = zero, state_out [N][2][H], out [N][T][2H],
+ * state sized vs_lstm_state_floats(N, H).  Guarantees (a) and (c) there hold here; with K = 1 and a zero row bias it computes what
+ * vs_bilstm_recurrent_carry computes.  Refused: what vs_bilstm_recurrent_carry refuses, K < 1, N not a multiple of K. */
+int vs_bilstm_recurrent_carry_shared(const float* xg, const float* rowbias, int K, const float* packed_whh, float* state, float* out,
+                                     const float* state_in, float* state_out, int keep, int N, int T, int H, int math, void* stream);
 
 /* =============================================================================================
  * Training: forward that keeps what backward needs + the backward pass itself.

@@ -119,6 +119,8 @@ SIGNATURES = {
     "vs_bilstm_fwd_multi": (c_int, [POINTER(VsDims), POINTER(VsParams), _P, _P, c_int, _P, _P, c_size_t, _P, _P]),
     "vs_bilstm_fwd_carry": (c_int, [POINTER(VsDims), POINTER(VsParams), _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P]),
     "vs_bilstm_recurrent_carry": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vs_bilstm_fwd_carry_multi": (c_int, [POINTER(VsDims), POINTER(VsParams), _P, _P, c_int, _P, _P, c_int, _P, c_size_t, _P, _P]),
+    "vs_bilstm_recurrent_carry_shared": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "vs_conv_stack_fwd": (c_int, [POINTER(VsDims), POINTER(VsParams), _P, c_int, c_int, _P, c_size_t, _P, _P]),
     "vs_bilstm_fwd": (c_int, [POINTER(VsDims), POINTER(VsParams), _P, _P, _P, c_size_t, _P, _P]),
     "vs_head_fwd": (c_int, [POINTER(VsDims), POINTER(VsParams), _P, _P, c_size_t, _P, _P, _P]),

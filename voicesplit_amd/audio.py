@@ -184,9 +184,14 @@ def separate_speakers(model, wav: torch.Tensor, dvecs: torch.Tensor, audio_cfg) 
 def separate_speakers_with_reference(model, encoder, wav: torch.Tensor, ref_wavs, audio_cfg) -> torch.Tensor:
     """``separate_speakers`` with the d-vectors computed here: ref_wavs[b] = a list of K reference waveforms (1-D, the same K for
     every mixture; lengths as in ``separate_with_reference``), embedded in one ``encoder.embed_many`` call."""
+    return separate_speakers(model, wav, _embed_references(encoder, ref_wavs, wav.shape[0], audio_cfg), audio_cfg)
+
+
+def _embed_references(encoder, ref_wavs, B: int, audio_cfg) -> torch.Tensor:
+    """d-vectors [B, K, emb_dim] of B lists of K reference waveforms each, in one ``encoder.embed_many`` call."""
     from .speaker import logmel
-    if len(ref_wavs) != wav.shape[0]:
-        raise ValueError(f"{len(ref_wavs)} lists of reference waveforms for {wav.shape[0]} mixtures")
+    if len(ref_wavs) != B:
+        raise ValueError(f"{len(ref_wavs)} lists of reference waveforms for {B} mixtures")
     K = len(ref_wavs[0]) if len(ref_wavs) else 0
     if K < 1 or any(len(r) != K for r in ref_wavs):
         raise ValueError(f"every mixture needs the same number K >= 1 of reference waveforms, got {[len(r) for r in ref_wavs]}")
@@ -195,7 +200,7 @@ def separate_speakers_with_reference(model, encoder, wav: torch.Tensor, ref_wavs
     if not bool(valid.all()):
         short = [(i // K, i % K) for i, v in enumerate(valid.tolist()) if not v]
         raise ValueError(f"reference waveforms {short} (mixture, speaker) are shorter than one encoder window of {encoder.window} frames")
-    return separate_speakers(model, wav, dvec.view(wav.shape[0], K, -1).contiguous(), audio_cfg)
+    return dvec.view(B, K, -1).contiguous()
 
 
 class StreamingSeparator:
@@ -212,10 +217,16 @@ class StreamingSeparator:
     * iSTFT: the masked frames are inverted as one segment; the overlap-add of a sample within ``margin`` frames of a segment
       edge that is not a stream edge misses frames, so those samples are dropped and their frames are inverted again later.
 
-    A sample is returned once ``latency_samples`` more have been pushed (or at ``finish()``)."""
+    A sample is returned once ``latency_samples`` more have been pushed (or at ``finish()``).
+
+    Several enrolled speakers per stream: ``dvec [B, K, emb_dim]`` -> ``push`` / ``finish`` return ``[B, K, n]``; row [b, k] is the
+    stream b separated for ``dvec[b, k]``.  STFT, conv windows and the LSTM input GEMM run once per mixture (the K-speaker
+    ``StreamingMasker``); spectrogram and phase are kept once per mixture and repeated per speaker only for ``spec_to_wav``, as
+    in ``separate_speakers``.  ``latency_samples`` is that of one speaker.  ``with_reference`` embeds the K reference waveforms."""
 
     def __init__(self, model, dvec: torch.Tensor, audio_cfg, C: int, R: int, trace: bool = False):
         from .streaming import StreamingMasker
+        self.K = int(dvec.shape[1]) if dvec.dim() == 3 else None      # None: one speaker per stream, [B, n] out
         self.mask_trace = [] if trace else None  # trace: every block of mask rows, in order
         self.cfg = audio_cfg
         self.hop = int(audio_cfg["hop_length"])
@@ -227,9 +238,16 @@ class StreamingSeparator:
         self._hops = 0                           # pushed samples / hop
         self._frames = 0                         # STFT frames handed to the masker
         self._spec = self._phase = None          # frames [_s0, _frames)
-        self._mask = None                        # rows [_s0, _rows)
+        self._mask = None                        # rows [_s0, _rows); K speakers: [B*K, rows, F], row b*K + k
         self._s0 = self._rows = 0
         self._out = 0                            # returned samples / hop
+
+    @classmethod
+    def with_reference(cls, model, encoder, ref_wavs, audio_cfg, C: int, R: int, trace: bool = False):
+        """The K-speaker separator with the d-vectors computed here, once: ref_wavs[b] = a list of K reference waveforms (1-D, the
+        same K for every stream; lengths as in ``separate_with_reference``), embedded in one ``encoder.embed_many`` call, as
+        ``separate_speakers_with_reference`` does."""
+        return cls(model, _embed_references(encoder, ref_wavs, len(ref_wavs), audio_cfg), audio_cfg, C, R, trace=trace)
 
     @property
     def latency_samples(self) -> int:
@@ -277,20 +295,30 @@ class StreamingSeparator:
         if self.finished and self._frames:
             masks.append(self.masker.finish())
         for mk in masks:
-            if mk.shape[1]:
+            if mk.shape[-2]:
                 if self.mask_trace is not None:
                     self.mask_trace.append(mk)
+                if self.K is not None:       # [B, K, m, F] -> [B*K, m, F], row b*K + k
+                    mk = mk.reshape(-1, mk.shape[2], mk.shape[3])
                 self._mask = mk if self._mask is None else torch.cat((self._mask, mk), dim=1)
                 self._rows += mk.shape[1]
         # synthesis: samples [_out * hop, done * hop) are exact now
         done = self._hops if self.finished else self._rows - 1 - m
+        B = self._wav.shape[0]
         if done <= self._out or self._mask is None:
-            return self._wav.new_empty(self._wav.shape[0], 0)
+            return self._wav.new_empty(B, 0) if self.K is None else self._wav.new_empty(B, self.K, 0)
         fa = max(0, self._out - m)
         lo, hi = fa - self._s0, self._rows - self._s0
-        wav = spec_to_wav(self._spec[:, lo:hi].contiguous(), self._phase[:, lo:hi].contiguous(), self.cfg,
+
+        def rows(t):             # the mixture's frames, K speakers: repeated per speaker, [B*K, n, F] with row b*K + k = mixture b
+            t = t[:, lo:hi]
+            return t.contiguous() if self.K is None else t[:, None].expand(B, self.K, *t.shape[1:]).reshape(B * self.K, *t.shape[1:]).contiguous()
+
+        wav = spec_to_wav(rows(self._spec), rows(self._phase), self.cfg,
                           mask=self._mask[:, lo:hi].contiguous())                        # samples [fa * hop, (_rows - 1) * hop)
         out = wav[:, (self._out - fa) * hop:(done - fa) * hop]
+        if self.K is not None:
+            out = out.reshape(B, self.K, -1)
         self._out = done
         s0 = max(0, self._out - m)
         self._spec, self._phase, self._mask = self._spec[:, s0 - self._s0:], self._phase[:, s0 - self._s0:], self._mask[:, s0 - self._s0:]
@@ -303,7 +331,9 @@ class StreamingSeparatorAtRate:
     ``push(samples [B, k])`` for any k returns the separated samples that became final ([B, m], m >= 0, at ``sample_rate``),
     ``finish()`` the rest; the concatenation has exactly the pushed length.  A ``resample.StreamingResampler`` on each side; the
     converted samples wait here until a multiple of hop_length is pending (at ``finish()`` the last block is padded with zeros).
-    What it returns is ``StreamingSeparator`` fed the whole converted stream (so padded), converted back and cut."""
+    What it returns is ``StreamingSeparator`` fed the whole converted stream (so padded), converted back and cut.
+    ``dvec [B, K, emb_dim]``: ``[B, K, m]`` out; the conversion back runs on the B*K rows (a row's output does not depend on the
+    others: the resampler's own guarantee)."""
 
     def __init__(self, model, dvec: torch.Tensor, audio_cfg, C: int, R: int, sample_rate: int):
         from .resample import StreamingResampler
@@ -311,6 +341,7 @@ class StreamingSeparatorAtRate:
         self.sample_rate, self.own_rate = int(sample_rate), own
         self.hop = int(audio_cfg["hop_length"])
         self.sep = StreamingSeparator(model, dvec, audio_cfg, C, R)
+        self.K = self.sep.K
         self.down = StreamingResampler(self.sample_rate, own, dvec.device, resampler=resampler(self.sample_rate, own, dvec.device))
         self.up = StreamingResampler(own, self.sample_rate, dvec.device, resampler=resampler(own, self.sample_rate, dvec.device))
         self.finished = False
@@ -331,14 +362,18 @@ class StreamingSeparatorAtRate:
             self._pending = torch.nn.functional.pad(self._pending, (0, -self._pending.shape[1] % self.hop))
         n = self._pending.shape[1] // self.hop * self.hop
         block, self._pending = self._pending[:, :n].contiguous(), self._pending[:, n:]
-        outs = [self.up.push(self.sep.push(block))] if n else []
+
+        def flat(t):             # [B, K, n] -> the up-resampler's rows [B*K, n]
+            return t if self.K is None else t.reshape(-1, t.shape[2])
+
+        outs = [self.up.push(flat(self.sep.push(block)))] if n else []
         if last:
-            outs += [self.up.push(self.sep.finish()), self.up.finish()]
+            outs += [self.up.push(flat(self.sep.finish())), self.up.finish()]
         if not outs:
-            return x.new_empty(x.shape[0], 0)
+            return x.new_empty(x.shape[0], 0) if self.K is None else x.new_empty(x.shape[0], self.K, 0)
         out = torch.cat(outs, dim=1)[:, :self._pushed - self._returned]
         self._returned += out.shape[1]
-        return out
+        return out if self.K is None else out.reshape(x.shape[0], self.K, -1)
 
     def push(self, samples: torch.Tensor) -> torch.Tensor:
         if self.finished:

@@ -560,7 +560,8 @@ int bilstm(const Fwd& f, const float* feat, const float* dvec, float* lstm_out, 
   ProfScope ps(VS_PROF_LSTM_REC, f.stream);
   // (lengths: the input GEMM above ran over all B*T rows; the recurrence keeps the rows behind an item's end out of its state)
   if (multi)
-    return vs_bilstm_recurrent_impl(xg, packed, multi->lstm_state, lstm_out, nullptr, nullptr, NS, T, H, f.stream, d->math, f.lengths, dvbias, multi->K);
+    return vs_bilstm_recurrent_impl(xg, packed, multi->lstm_state, lstm_out, nullptr, nullptr, NS, T, H, f.stream, d->math, f.lengths, dvbias, multi->K,
+                                    f.carry);
   return vs_bilstm_recurrent_impl(xg, packed, f.at<float>(L.lstm_state), lstm_out, nullptr, nullptr, B, T, H, f.stream, d->math, f.lengths,
                                   nullptr, 1, f.carry);
 }
@@ -799,6 +800,21 @@ int vs_bilstm_fwd_carry(const vs_dims* d, const vs_params* p, const float* feat,
   if (int rc = check_ws(d, ws, ws_bytes, &L)) return rc;
   const VsLstmCarry carry{state_in, state_out, keep};
   return bilstm(make_fwd(d, p, ws, L, VS_ACT_NONE, VS_BN_EVAL, (hipStream_t)stream, nullptr, nullptr, nullptr, &carry), feat, dvec, lstm_out, false);
+}
+
+// one chunk of a stream for K enrolled speakers per mixture: the input GEMM once without row bias, the carry x shared-input recurrence
+// over the B*K sequences (see the header)
+int vs_bilstm_fwd_carry_multi(const vs_dims* d, const vs_params* p, const float* feat, const float* dvecs, int K,
+                              const float* state_in, float* state_out, int keep,
+                              void* ws, size_t ws_bytes, float* lstm_out, void* stream) {
+  if (int rc = check_multi(d, dvecs, K, "bilstm_fwd_carry_multi")) return rc;
+  if (int rc = vs_lstm_carry_check(d->math, d->H, d->T, keep, state_out, "bilstm_fwd_carry_multi")) return rc;
+  VS_REQUIRE(feat && lstm_out, "bilstm_fwd_carry_multi: NULL argument");
+  MultiLayout M;
+  if (int rc = check_multi_ws(d, K, ws, ws_bytes, &M)) return rc;
+  const MultiBufs mb = multi_bufs(ws, M, K);
+  const VsLstmCarry carry{state_in, state_out, keep};
+  return bilstm(make_fwd(d, p, ws, M.base, VS_ACT_NONE, VS_BN_EVAL, (hipStream_t)stream, nullptr, nullptr, &mb, &carry), feat, dvecs, lstm_out, false);
 }
 
 int vs_head_fwd(const vs_dims* d, const vs_params* p, const float* lstm_out, void* ws, size_t ws_bytes,

@@ -553,6 +553,12 @@ struct LstmSharedIn {
 // forward outputs over the caller's look-ahead frames).  The h handed out is the fp32 value the exchange store rounds, and the seeding
 // pass rounds it the same way: two calls over [0, a) and [a, T) give the forward half of one call over [0, T) bit for bit.  Hand-off,
 // re-arming, spins and error word are the kernel's own; !CARRY is the kernel as it was (cy unused).
+//
+// CARRY x SHARED (several enrolled speakers from one live mixture, vs_bilstm_recurrent_carry_shared): both of the above, per column.
+// Column n = m*K + k reads xg at mixture n / K and adds its own resident row bias (SHARED); its forward direction starts from
+// state_in[n] and hands its state to state_out[n] (CARRY): state, exchange slots and outputs are indexed by the column, only the xg row
+// by the mixture.  The seeding pass runs over the N columns.  No other line differs, so what makes the carried state exact -- the h
+// handed out is the fp32 value the exchange store rounds, the seed rounds it with lstm16_pack_h<NP, true> -- holds per column.
 struct LstmCarry {
   const float* state_in;  // [B][2][H] fp32: h and c of the forward direction in front of frame 0, or NULL: zero (only c is read here)
   float* state_out;       // [B][2][H] fp32: h and c of the forward direction behind frame keep - 1
@@ -835,6 +841,20 @@ extern "C" int vs_bilstm_recurrent_carry(const float* xg, const float* packed_wh
   return vs_bilstm_recurrent_impl(xg, packed_whh, state, out, nullptr, nullptr, B, T, H, (hipStream_t)stream, math, nullptr, nullptr, 1, &carry);
 }
 
+// the raw carry x shared-input recurrence: N = M * K sequences, sequence n reads row n / K of xg (see the header)
+extern "C" int vs_bilstm_recurrent_carry_shared(const float* xg, const float* rowbias, int K, const float* packed_whh, float* state, float* out,
+                                                const float* state_in, float* state_out, int keep, int N, int T, int H, int math, void* stream) {
+  const char* what = "bilstm_recurrent_carry_shared";
+  VS_REQUIRE(math == VS_MATH_CODE_FP32 || math == VS_MATH_CODE_F16X3 || math == VS_MATH_CODE_BF16, "%s: unknown math %d", what, math);
+  VS_REQUIRE(N > 0 && T > 0 && H > 0 && H % 8 == 0, "%s: bad shape N=%d T=%d H=%d (H must be a multiple of 8)", what, N, T, H);
+  VS_REQUIRE(K >= 1, "%s: K=%d speakers per mixture (K >= 1)", what, K);
+  VS_REQUIRE(N % K == 0, "%s: N=%d sequences are not a multiple of K=%d", what, N, K);
+  if (int rc = vs_lstm_carry_check(math, H, T, keep, state_out, what)) return rc;
+  VS_REQUIRE(xg && rowbias && packed_whh && state && out, "%s: NULL argument", what);
+  const VsLstmCarry carry{state_in, state_out, keep};
+  return vs_bilstm_recurrent_impl(xg, packed_whh, state, out, nullptr, nullptr, N, T, H, (hipStream_t)stream, math, nullptr, rowbias, K, &carry);
+}
+
 namespace {
 // A persistent launch whose spin gave up (a workgroup was not resident: the error word is 1) has produced garbage.
 // The word is only read by callers that ask (vs_lstm_status), so the result itself is made unusable: NaN in the first
@@ -846,14 +866,16 @@ __global__ void lstm_poison_kernel(const unsigned* __restrict__ err, float* __re
   if (i < n) out[i] = __uint_as_float(0x7fc00000u);
 }
 
-// The ten instances of lstm16_tagged_kernel.  The carry form takes neither lengths nor a row bias: no CARRY x RAGGED / SHARED instance.
+// The twelve instances of lstm16_tagged_kernel.  The carry form takes a row bias (CARRY x SHARED) but no lengths: no CARRY x RAGGED
+// instance.
 const void* lstm16_tagged_instance(int np, bool ragged, bool shared, bool carry) {
 #define VS_TAGGED(...) reinterpret_cast<const void*>(&lstm16_tagged_kernel<__VA_ARGS__>)
   static const void* const plain[2][2][2] = {{{VS_TAGGED(1, false, false), VS_TAGGED(1, false, true)}, {VS_TAGGED(1, true, false), VS_TAGGED(1, true, true)}},
                                              {{VS_TAGGED(2, false, false), VS_TAGGED(2, false, true)}, {VS_TAGGED(2, true, false), VS_TAGGED(2, true, true)}}};
-  static const void* const carried[2] = {VS_TAGGED(1, false, false, true), VS_TAGGED(2, false, false, true)};
+  static const void* const carried[2][2] = {{VS_TAGGED(1, false, false, true), VS_TAGGED(1, false, true, true)},
+                                            {VS_TAGGED(2, false, false, true), VS_TAGGED(2, false, true, true)}};
 #undef VS_TAGGED
-  return carry ? carried[np - 1] : plain[np - 1][ragged][shared];
+  return carry ? carried[np - 1][shared] : plain[np - 1][ragged][shared];
 }
 
 // What the tagged persistent recurrence in eval mode alone serves, and how its two refusals read: anything else refuses such a call,
@@ -864,7 +886,7 @@ const LstmTaggedOnly kSharedOnly{"shared-input recurrence",
                                  "the shared-input recurrence (several speakers per mixture) is the tagged persistent recurrence in eval mode", "",
                                  "do not offer it"};
 const LstmTaggedOnly kCarryOnly{"carried state", "the carried state is served by the tagged persistent recurrence in eval mode alone",
-                                ", no lengths, one speaker per mixture", "start from a zero state"};
+                                ", no lengths", "start from a zero state"};
 int lstm_refuse_not_tagged(const LstmTaggedOnly& f, int HQ, int cus) {
   vs_set_error("lstm: %s (dims.math F16X3 or BF16, H <= %d, 2*H/8 = %d workgroups <= %d CUs, vs_set_lstm_kernel 0 or 2%s); VS_MATH_FP32, the flag "
                "kernel and the per-step kernels %s", f.claim, 64 * kMaxC, 2 * HQ, cus, f.also, f.tail);
@@ -888,7 +910,8 @@ int vs_lstm_poison_impl(const unsigned* err, float* out, long long n, hipStream_
 // rowbias != NULL: the shared-input form (lstm16_tagged_kernel<.., SHARED>): B sequences n = m*K + k read xg [B / K][T][8H] at mixture
 // n / K and add rowbias [B][8H]; lengths, when given, are per mixture [B / K]; out [B][T][2H]
 // carry != NULL: the carry form (lstm16_tagged_kernel<.., CARRY>): the forward direction starts from carry->state_in and hands its
-// state behind frame carry->keep - 1 to carry->state_out
+// state behind frame carry->keep - 1 to carry->state_out.  With rowbias too (lstm16_tagged_kernel<.., SHARED, CARRY>) the state is per
+// sequence, [B][2][H] with B = the B * K of the caller; with lengths it is refused
 int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, float* out, float* gates_save, float* c_save,
                              int B, int T, int H, hipStream_t stream, int math, const int* lengths, const float* rowbias, int K,
                              const VsLstmCarry* carry) {
@@ -911,7 +934,7 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
   const bool tagged_eval = tagged && !gates_save && !c_save;
   if (lengths && !tagged_eval) return lstm_refuse_not_tagged(kLengthsOnly, HQ, cus);
   if (rowbias && !tagged_eval) return lstm_refuse_not_tagged(kSharedOnly, HQ, cus);
-  if (carry && !(tagged_eval && !lengths && !rowbias)) return lstm_refuse_not_tagged(kCarryOnly, HQ, cus);
+  if (carry && !(tagged_eval && !lengths)) return lstm_refuse_not_tagged(kCarryOnly, HQ, cus);
   if (tagged) VS_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(state + per), (int)kSentinel, 3 * per, stream));
   if (carry && carry->state_in) {          // h_0 of the forward direction into exchange buffer 0 (zeroed above), in the kernel's operand form
     const long long n = (long long)B * HQ;

@@ -281,7 +281,7 @@ int vs_bilstm_recurrent_impl(const float* xg, const float* wp, float* state, flo
                              const int* lengths = nullptr /* device [B]: h = c = 0 while t >= lengths[b]; only the tagged persistent kernel takes them */,
                              const float* rowbias = nullptr /* [B][8H]: the shared-input form, xg [B / K][T][8H] and lengths [B / K] (lstm_fwd.hip) */,
                              int K = 1,
-                             const VsLstmCarry* carry = nullptr /* the carry form: forward direction from / to a caller-held state (lstm_fwd.hip) */);
+                             const VsLstmCarry* carry = nullptr /* the carry form: forward direction from / to a caller-held state, with rowbias: one per sequence; never with lengths (lstm_fwd.hip) */);
 // the refusals of the carry form that need no device (argument ranges, arithmetic, hidden size, vs_set_lstm_kernel)
 int vs_lstm_carry_check(int math, int H, int T, int keep, const float* state_out, const char* what);
 // what vs_set_lstm_kernel last set (the one copy of the mode lives in lstm_fwd.hip)

@@ -289,7 +289,8 @@ class _MaskNet(nn.Module):
         """(conv_stage, carry_stage, head_stage) for ``streaming.StreamingMasker``: the conv stack on a window of a stream, the
         BiLSTM over [chunk | look-ahead] with its forward direction carried from chunk to chunk (``ops.bilstm_carry``) and the head
         on the chunk's rows, all in eval mode, all straight into the C ABI stage entry points.  want_logits: the head stage
-        returns (mask, logits)."""
+        returns (mask, logits).  With d-vectors [B, K, emb_dim] the carry stage is ``ops.bilstm_carry_multi`` (K enrolled speakers
+        per stream: lstm_out [B, K, n, 2H], state [B*K, 2, H]) and the head stage takes and returns the K axis."""
         if self.training:
             raise RuntimeError("stream separation runs in eval mode (BatchNorm running statistics, no tape): call model.eval() first")
         sd = {k: v.detach() for k, v in self._tensors().items()}
@@ -298,9 +299,18 @@ class _MaskNet(nn.Module):
             return ops.conv_stack(sd, xw.contiguous(), self._dims(xw.shape[0], xw.shape[1]), self.conv_act)
 
         def carry_stage(feat, dvec, state, keep):
-            return ops.bilstm_carry(sd, feat.contiguous(), dvec.contiguous(), self._dims(feat.shape[0], feat.shape[1]), state, keep)
+            dims = self._dims(feat.shape[0], feat.shape[1])
+            if dvec.dim() == 3:
+                # [B, K, emb_dim]: K enrolled speakers per stream -> lstm_out [B, K, n, 2H], state [B*K, 2, H]; one input GEMM per
+                # chunk, the carry x shared-input recurrence over the B*K sequences
+                return ops.bilstm_carry_multi(sd, feat.contiguous(), dvec.contiguous(), dims, state, keep)
+            return ops.bilstm_carry(sd, feat.contiguous(), dvec.contiguous(), dims, state, keep)
 
         def head_stage(lstm_out):
+            if lstm_out.dim() == 4:          # [B, K, n, 2H]: the head over the B*K rows -> [B, K, n, F2] (logits likewise)
+                B, K, n = lstm_out.shape[:3]
+                out = ops.head(sd, lstm_out.contiguous().view(B * K, n, -1), self._dims(B * K, n), want_logits=want_logits)
+                return tuple(o.view(B, K, n, -1) for o in out) if want_logits else out.view(B, K, n, -1)
             return ops.head(sd, lstm_out.contiguous(), self._dims(lstm_out.shape[0], lstm_out.shape[1]), want_logits=want_logits)
 
         return conv_stage, carry_stage, head_stage

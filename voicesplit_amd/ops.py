@@ -370,6 +370,29 @@ def bilstm_carry(sd, feat, dvec, dims: VsDims, state=None, keep: Optional[int] =
     return out, state_out
 
 
+def bilstm_carry_multi(sd, feat, dvecs, dims: VsDims, state=None, keep: Optional[int] = None, workspace=None):
+    """``bilstm_carry`` for K enrolled speakers per stream (vs_bilstm_fwd_carry_multi): feat [B, T, 8F] (once per mixture), dvecs
+    [B, K, E]; one input GEMM per mixture, the carry x shared-input recurrence over the B*K sequences n = b*K + k, each continuing
+    from its own row of ``state`` [B*K, 2, H] (h, then c; None: zero).  Returns (lstm_out [B, K, T, 2H], state behind frame
+    keep - 1 [B*K, 2, H]); keep defaults to T."""
+    lib = _lib.load()
+    _dev_check(feat, "feat")
+    _dev_check(dvecs, "speaker_embeddings")
+    _check_multi_dvecs(dvecs, feat.shape[0], dims)
+    K = int(dvecs.shape[1])
+    keep = dims.T if keep is None else int(keep)
+    state = _check_carry_state(state, dims.B * K, dims.H, feat.device)
+    params = pack_params(sd)
+    ws = workspace if workspace is not None else get_multi_workspace(dims, K, feat.device)
+    out = torch.empty(dims.B, K, dims.T, 2 * dims.H, dtype=torch.float32, device=feat.device)
+    state_out = torch.empty(dims.B * K, 2, dims.H, dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device):
+        rc = lib.vs_bilstm_fwd_carry_multi(ctypes.byref(dims), ctypes.byref(params), _p(feat), _p(dvecs), K, _p(state), _p(state_out), keep,
+                                           _p(ws), ws.numel(), _p(out), _stream())
+    check(rc, "vs_bilstm_fwd_carry_multi")
+    return out, state_out
+
+
 def zero_tail_rows(t: torch.Tensor, lengths) -> torch.Tensor:
     """In place: rows t[b, lengths[b]:] := 0 of a contiguous [B, T, ...] tensor (vs_zero_tail_rows; unit-test surface)."""
     lib = _lib.load()
@@ -524,6 +547,37 @@ def bilstm_recurrent_carry(xg, w_hh_f, w_hh_b, math, state=None, keep: Optional[
         check(lib.vs_bilstm_recurrent_carry(_p(xg), _p(packed), _p(scratch), _p(out), _p(state_in), _p(state_out), keep, B, T, H, math,
                                             _stream()), "vs_bilstm_recurrent_carry")
     _lstm_check_err(scratch, scratch.numel() - 64, "vs_bilstm_recurrent_carry")
+    return out, state_out
+
+
+def bilstm_recurrent_carry_shared(xg, rowbias, K: int, w_hh_f, w_hh_b, math, state=None, keep: Optional[int] = None, state_out=None):
+    """The raw carry x shared-input recurrence (vs_bilstm_recurrent_carry_shared): xg [M,T,8H] WITHOUT row bias, rowbias [N,8H] with
+    N = M*K; sequence n = m*K + k reads xg[m], adds rowbias[n] and continues from ``state`` [N,2,H] (h, then c; None: zero) ->
+    (out [N,T,2H], state behind frame keep - 1 [N,2,H]); keep defaults to T.  state_out: the buffer to hand the state to (it may
+    be ``state`` itself), else a new one."""
+    lib = _lib.load()
+    for n, t in (("xg", xg), ("rowbias", rowbias), ("w_hh_f", w_hh_f), ("w_hh_b", w_hh_b)):
+        _dev_check(t, n)
+    math = MATH_CODES[math] if isinstance(math, str) else int(math)
+    M, T, H8 = xg.shape
+    H = H8 // 8
+    N = int(rowbias.shape[0])
+    if rowbias.dim() != 2 or rowbias.shape[1] != H8:
+        raise ValueError(f"rowbias must be [N, 8H = {H8}], got {tuple(rowbias.shape)}")
+    if int(K) >= 1 and N != M * int(K):
+        raise ValueError(f"rowbias has {N} rows, xg has M = {M} rows shared by K = {K} sequences each")
+    keep = T if keep is None else int(keep)
+    state_in = _check_carry_state(state, N, H, xg.device)
+    packed = torch.empty(lib.vs_lstm_packed_floats(H), dtype=torch.float32, device=xg.device)
+    scratch = torch.empty(lib.vs_lstm_state_floats(N, H), dtype=torch.float32, device=xg.device)
+    out = torch.empty(N, T, 2 * H, dtype=torch.float32, device=xg.device)
+    state_out = _check_carry_state(state_out, N, H, xg.device) if state_out is not None else \
+        torch.empty(N, 2, H, dtype=torch.float32, device=xg.device)
+    with torch.cuda.device(xg.device):
+        check(lib.vs_lstm_pack_math(_p(w_hh_f), _p(w_hh_b), _p(packed), H, math, _stream()), "vs_lstm_pack_math")
+        check(lib.vs_bilstm_recurrent_carry_shared(_p(xg), _p(rowbias), int(K), _p(packed), _p(scratch), _p(out), _p(state_in), _p(state_out),
+                                                   keep, N, T, H, math, _stream()), "vs_bilstm_recurrent_carry_shared")
+    _lstm_check_err(scratch, scratch.numel() - 64, "vs_bilstm_recurrent_carry_shared")
     return out, state_out
 
 

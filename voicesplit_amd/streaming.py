@@ -239,15 +239,23 @@ class StreamingMasker:
     the object.  ``push(frames [B, n, F])`` returns the mask rows that became due, [B, m, F2] with m >= 0 a multiple of ``C``;
     ``finish()`` returns the rest.  Kept between calls: the input frames the next conv window needs, the finalised features of the
     chunks not yet out, the forward state.  ``trace=True`` keeps every chunk's ``lstm_out`` rows (and logits) in ``self.trace``.
+
+    Several enrolled speakers per stream: ``dvec [B, K, E]``.  Input frames, conv windows, finalised features and the plan stay per
+    mixture (one conv window per arrival, whatever K); ``carry_stage`` is given the 3-D d-vectors and returns ``lstm_out [B, K, n,
+    2H]`` with the state of the B*K sequences ``[B*K, 2, H]``, ``head_stage`` takes ``[B, K, n, 2H]`` and returns ``[B, K, n, F2]``,
+    and ``push`` / ``finish`` return ``[B, K, m, F2]``; trace rows carry the K axis.  Emission times and ``latency_frames`` are those
+    of one speaker.
     """
 
     def __init__(self, conv_stage: Callable, carry_stage: Callable, head_stage: Callable, dvec: torch.Tensor, C: int, R: int,
                  halo: int = CONV_RECEPTIVE_HALO, trace: bool = False):
-        if dvec.dim() != 2:
-            raise ValueError(f"dvec must be [B, E], got {tuple(dvec.shape)}")
+        if dvec.dim() not in (2, 3) or 0 in dvec.shape:
+            raise ValueError(f"dvec must be [B, E], or [B, K, E] with K >= 1 speakers per stream, got {tuple(dvec.shape)}")
         plan_stream(0, False, C, R, halo)                      # range checks
         self.conv_stage, self.carry_stage, self.head_stage = conv_stage, carry_stage, head_stage
         self.dvec = dvec.contiguous()
+        self.K = int(dvec.shape[1]) if dvec.dim() == 3 else None      # None: one speaker per stream, outputs without a K axis
+        self._tdim = 1 if self.K is None else 2                        # the time axis of lstm_out and of the masks
         self.C, self.R, self.halo = int(C), int(R), int(halo)
         self.pushed = self.feat_done = self.chunks_done = 0
         self.finished = False
@@ -302,15 +310,16 @@ class StreamingMasker:
             for k, lo, hi, e in plan.chunks:
                 seg = self._feat[:, lo - self._f0:e - self._f0].contiguous()
                 lstm_out, self._state = self.carry_stage(seg, self.dvec, self._state, hi - lo)
-                rows = lstm_out[:, :hi - lo].contiguous()
+                rows = lstm_out.narrow(self._tdim, 0, hi - lo).contiguous()
                 out = self.head_stage(rows)
                 mask, logits = out if isinstance(out, tuple) else (out, None)
                 if self.trace is not None:
                     self.trace.append({"chunk": k, "lo": lo, "hi": hi, "e": e, "lstm_out": rows, "logits": logits})
                 pieces.append(mask)
-                self._out_dim = mask.shape[2]
+                self._out_dim = mask.shape[-1]
                 self._feat, self._f0 = self._feat[:, hi - self._f0:], hi
                 self.chunks_done = k + 1
         if pieces:
-            return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
-        return self._x.new_empty(self._x.shape[0], 0, self._out_dim if self._out_dim is not None else self._x.shape[2])
+            return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=self._tdim)
+        lead = (self._x.shape[0],) if self.K is None else (self._x.shape[0], self.K)
+        return self._x.new_empty(*lead, 0, self._out_dim if self._out_dim is not None else self._x.shape[2])
