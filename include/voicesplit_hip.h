@@ -772,6 +772,28 @@ size_t vs_sdr_workspace_bytes(int B, long long N);
 int vs_sdr(const float* ref, const float* est, int B, long long N, double* sdr, int* status,
            void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-source BSS-eval, mir_eval.separation.bss_eval_sources(reference, estimate, compute_permutation): per item K
+ * references s_j and K estimates e_q of N samples, the 512-tap filter as above, M = N + 511:
+ *   P_all,q = projection of e_q on all K references delayed 0..511 (block-Toeplitz Gram matrix of K x K blocks, solved by
+ *             the block Levinson recursion; never formed);  P_jq = vs_sdr's projection of e_q on s_j alone
+ *   SDR[q][j] = |P_jq|^2 / |[e_q,0] - P_jq|^2,  SIR[q][j] = |P_jq|^2 / |P_all,q - P_jq|^2,
+ *   SAR[q][j] = |P_all,q|^2 / |[e_q,0] - P_all,q|^2,  each 10 log10, +inf when the denominator is exactly 0.
+ * compute_permutation != 0: all K x K pairs; popt maximises sum_j SIR[popt[j]][j] over the permutations in lexicographic
+ * order (itertools.permutations), the first maximum wins, the sum taken for j = 0..K-1 in fp64; sdr[j] = SDR[popt[j]][j],
+ * likewise sir and sar, perm = popt.  compute_permutation == 0: only the pairs (j, j), perm = 0..K-1.
+ * status per item: 0 = ok; 1 = a reference or estimate row of the item is all zero; 2 = a solve failed (a singular or
+ * non-finite R[0], I - e_B e_F or I - e_F e_B of the block recursion, or a prediction error <= 0 of a single-source solve).
+ * An item with status != 0 gets NaN everywhere and perm -1.  fp64 throughout, sums in an order fixed by (K, N) alone: bitwise
+ * reproducible, and an item's values do not depend on B.  K = 1: sdr is bit-equal to vs_sdr's, sir = +inf, sar = sdr. */
+/* bytes of workspace vs_bss_eval needs; 0 for arguments out of range (B, N as vs_sdr, 1 <= K <= 6) */
+size_t vs_bss_eval_workspace_bytes(int B, int K, long long N);
+/* ref, est: [B][K][N] fp32; sdr, sir, sar: [B][K] doubles (dB); perm: [B][K] ints; status: [B] ints; pairs: NULL or
+ * [B][3][K][K] doubles indexed [criterion sdr/sir/sar][estimate][reference], off-diagonal NaN when compute_permutation == 0.
+ * ws: vs_bss_eval_workspace_bytes(B, K, N) bytes, 256-byte aligned.  All launches on `stream`, no synchronisation. */
+int vs_bss_eval(const float* ref, const float* est, int B, int K, long long N, int compute_permutation,
+                double* sdr, double* sir, double* sar, int* perm, int* status, double* pairs,
+                void* workspace, size_t workspace_bytes, void* stream);
+
 /* =============================================================================================
  * ABI 11.  The GE2E speaker encoder, inference only: reference audio -> the d-vector `dvec` that vs_forward* take
  * (notebooks/GE2E-Seungwonpark-ExtractSpeakerEmbedding-...py with ap.get_mel, utils/audio_processor.py:460-467, in front):

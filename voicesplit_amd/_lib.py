@@ -221,6 +221,8 @@ SIGNATURES = {
     # evaluation metric
     "vs_sdr_workspace_bytes": (c_size_t, [c_int, c_longlong]),
     "vs_sdr": (c_int, [_P, _P, c_int, c_longlong, _P, _P, _P, c_size_t, _P]),
+    "vs_bss_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_longlong]),
+    "vs_bss_eval": (c_int, [_P, _P, c_int, c_int, c_longlong, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     # speaker encoder
     "vs_speaker_prepared_bytes": (c_size_t, [POINTER(VsSpeakerDims)]),
     "vs_speaker_prepare": (c_int, [POINTER(VsSpeakerDims), POINTER(VsSpeakerParams), _P, c_size_t, _P]),

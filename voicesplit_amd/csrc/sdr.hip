@@ -22,25 +22,9 @@
 
 #include "../../include/voicesplit_hip.h"
 #include "vs_internal.h"
+#include "bss_common.h"
 
 namespace {
-
-constexpr int kFlen = 512;
-// correlation pass
-constexpr int kCorrTile = 2048;                       // samples of n per tile
-constexpr int kCorrStage = kCorrTile + kFlen + 16;    // + lags up to 511 + the window's read-ahead
-constexpr int kCorrLds = kCorrStage + (kCorrStage >> 3) + 1;
-constexpr int kSlot = 1032;                           // r[512], D[512], sum e^2, pad: doubles per partial
-// projection pass
-constexpr int kProjTile = 4096;                       // outputs of P per tile, 16 per lane
-constexpr int kProjStage = kProjTile + kFlen;         // s[m0 - 512 .. m0 + 4096)
-constexpr int kProjLds = kProjStage + (kProjStage >> 4) + 1;
-constexpr int kMaxChunks = 1024;                      // chunks per row at most (longer rows: several tiles per workgroup)
-
-// LDS index with one pad double every 8 (correlation: lanes 8 doubles apart -> 9) / every 16 (projection: 16 -> 17), so
-// that the 32 lanes of a ds_read_b64 group hit 32 distinct bank pairs
-__device__ __forceinline__ int pos8(int m) { return m + (m >> 3); }
-__device__ __forceinline__ int pos16(int m) { return m + (m >> 4); }
 
 struct SdrLayout {
   long long corr_tiles, corr_tpw, corr_chunks;
@@ -48,17 +32,11 @@ struct SdrLayout {
   size_t corr, rd, coef, proj, status, total;        // byte offsets into the workspace
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 SdrLayout sdr_layout(int B, long long N) {
   SdrLayout L;
-  L.corr_tiles = (N + kCorrTile - 1) / kCorrTile;
-  L.corr_tpw = (L.corr_tiles + kMaxChunks - 1) / kMaxChunks;
-  L.corr_chunks = (L.corr_tiles + L.corr_tpw - 1) / L.corr_tpw;
-  const long long M = N + kFlen - 1;
-  L.proj_tiles = (M + kProjTile - 1) / kProjTile;
-  L.proj_tpw = (L.proj_tiles + kMaxChunks - 1) / kMaxChunks;
-  L.proj_chunks = (L.proj_tiles + L.proj_tpw - 1) / L.proj_tpw;
+  const BssTiling T = bss_tiling(N);
+  L.corr_tiles = T.corr_tiles;  L.corr_tpw = T.corr_tpw;  L.corr_chunks = T.corr_chunks;
+  L.proj_tiles = T.proj_tiles;  L.proj_tpw = T.proj_tpw;  L.proj_chunks = T.proj_chunks;
   size_t off = 0;
   L.corr = off;   off = align256(off + (size_t)B * L.corr_chunks * kSlot * sizeof(double));
   L.rd = off;     off = align256(off + (size_t)B * kSlot * sizeof(double));
@@ -67,19 +45,6 @@ SdrLayout sdr_layout(int B, long long N) {
   L.status = off; off = align256(off + (size_t)B * sizeof(int));
   L.total = off;
   return L;
-}
-
-// fixed-order tree sum of v over the 256 threads of a workgroup; red: 256 doubles of LDS; result valid in thread 0
-__device__ double block_sum256(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
 }
 
 __global__ void __launch_bounds__(256) sdr_corr_kernel(const float* __restrict__ ref, const float* __restrict__ est, long long N,
@@ -98,139 +63,31 @@ __global__ void __launch_bounds__(256) sdr_corr_kernel(const float* __restrict__
   for (long long t = (long long)chunk * tpw; t < t_end; ++t) {
     const long long n0 = t * kCorrTile;
     __syncthreads();                                                    // the previous tile's readers are done
-    for (int i = tid; i < kCorrStage; i += 256) {
-      const long long g = n0 + i;
-      const double sv = g < N ? (double)s[g] : 0.0;
-      const double ev = g < N ? (double)e[g] : 0.0;
-      S[pos8(i)] = sv;
-      E[pos8(i)] = ev;
-      if (i < kCorrTile) ee += ev * ev;
-    }
+    corr_stage(s, N, n0, S, nullptr);
+    corr_stage(e, N, n0, E, &ee);
     __syncthreads();
-    const int nb0 = wave * (kCorrTile / 4);                             // this wave's quarter of the tile
-    const int k0 = lane * 8;                                            // this lane's lags k0 .. k0 + 7
-    double ws[8], we[8];                                                // slot (m - nb0 - k0) & 7 holds s[m], e[m]
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      ws[i] = S[pos8(nb0 + k0 + i)];
-      we[i] = E[pos8(nb0 + k0 + i)];
-    }
-    for (int nb = 0; nb < kCorrTile / 4; nb += 8) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int n = nb0 + nb + u;
-        const double a = S[pos8(n)];                                    // broadcast
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          ar[j] = fma(a, ws[(u + j) & 7], ar[j]);                       // s[n] s[n + k0 + j]
-          ad[j] = fma(a, we[(u + j) & 7], ad[j]);                       // s[n] e[n + k0 + j]
-        }
-        ws[u] = S[pos8(n + k0 + 8)];                                    // slot u: s[n + k0] is done, s[n + k0 + 8] next
-        we[u] = E[pos8(n + k0 + 8)];
-      }
-    }
+    corr_slide(S, S, E, wave, lane, ar, ad);
   }
   // the 4 waves' partials, summed in wave order (the staging area is free again)
   __syncthreads();
-  double* red = S;                                                      // [4][1024] fits in S + E (2 x 2898 doubles)
-  double* red2 = E;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = lane * 8 + j;
-    if (wave < 2) {
-      red[wave * 1024 + k] = ar[j];
-      red[wave * 1024 + 512 + k] = ad[j];
-    } else {
-      red2[(wave - 2) * 1024 + k] = ar[j];
-      red2[(wave - 2) * 1024 + 512 + k] = ad[j];
-    }
-  }
-  __syncthreads();
-  double* out = part + ((long long)row * gridDim.y + chunk) * kSlot;
-  for (int o = tid; o < 1024; o += 256)
-    out[o] = ((red[o] + red[1024 + o]) + red2[o]) + red2[1024 + o];
-  const double tot = block_sum256(ee, red);
-  if (tid == 0) out[1024] = tot;
+  corr_store(ar, ad, ee, S, E, part + ((long long)row * gridDim.y + chunk) * kSlot);    // [4][1024] fits in S + E (2 x 2898 doubles)
 }
 
 __global__ void __launch_bounds__(256) sdr_fold_kernel(const double* __restrict__ part, int chunks, double* __restrict__ rd) {
   const int row = blockIdx.x;
-  const double* p = part + (long long)row * chunks * kSlot;
-  for (int o = threadIdx.x; o < 1025; o += 256) {
-    double v = 0.0;
-    for (int c = 0; c < chunks; ++c) v += p[(long long)c * kSlot + o];
-    rd[(long long)row * kSlot + o] = v;
-  }
+  corr_fold(part + (long long)row * chunks * kSlot, chunks, rd + (long long)row * kSlot);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);          // commutative pairs: every lane ends with the same bits
-  return v;
-}
-
-// Levinson recursion for G C = D, G symmetric Toeplitz with first row r: the forward predictor a (a[0] = 1, G_i a = E e_0)
-// and the solution x grow one order per step; a reversed is the backward predictor, which extends x to the next order.
 __global__ void __launch_bounds__(64) sdr_levinson(const double* __restrict__ rd, double* __restrict__ coef, int* __restrict__ status) {
   __shared__ double r[kFlen], d[kFlen], a[kFlen], x[kFlen];
   const int row = blockIdx.x, lane = threadIdx.x;
   const double* src = rd + (long long)row * kSlot;
-  for (int j = lane; j < kFlen; j += 64) {
-    r[j] = src[j];
-    d[j] = src[kFlen + j];
-    a[j] = 0.0;
-    x[j] = 0.0;
-  }
   const double r0 = src[0], ee = src[1024];
   if (!(r0 > 0.0) || !(ee > 0.0)) {                                     // all-zero reference or estimate row
     if (lane == 0) status[row] = 1;
     return;
   }
-  __syncthreads();
-  if (lane == 0) {
-    a[0] = 1.0;
-    x[0] = d[0] / r0;
-  }
-  __syncthreads();
-  double Err = r0;
-  int fail = 0;
-  for (int i = 1; i < kFlen; ++i) {
-    double pa = 0.0, px = 0.0;
-    for (int j = lane; j < i; j += 64) {
-      const double rr = r[i - j];
-      pa = fma(a[j], rr, pa);
-      px = fma(x[j], rr, px);
-    }
-    pa = wave_sum(pa);
-    px = wave_sum(px);
-    const double k = -pa / Err;
-    double t[kFlen / 64];
-#pragma unroll
-    for (int m = 0; m < kFlen / 64; ++m) {
-      const int j = lane + 64 * m;
-      if (j <= i) t[m] = fma(k, a[i - j], a[j]);
-    }
-    __builtin_amdgcn_wave_barrier();                                    // every lane has read a before any lane writes it
-#pragma unroll
-    for (int m = 0; m < kFlen / 64; ++m) {
-      const int j = lane + 64 * m;
-      if (j <= i) a[j] = t[m];
-    }
-    __builtin_amdgcn_wave_barrier();
-    Err = Err * (1.0 - k * k);
-    if (!(Err > 0.0) || !isfinite(Err)) {                               // uniform across the wave
-      fail = 1;
-      break;
-    }
-    const double mu = (d[i] - px) / Err;
-#pragma unroll
-    for (int m = 0; m < kFlen / 64; ++m) {
-      const int j = lane + 64 * m;
-      if (j <= i) x[j] = fma(mu, a[i - j], x[j]);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-  if (fail) {
+  if (levinson512(src, src + kFlen, r, d, a, x, lane)) {
     if (lane == 0) status[row] = 2;
     return;
   }
@@ -258,28 +115,12 @@ __global__ void __launch_bounds__(256) sdr_proj_kernel(const float* __restrict__
   for (long long t = (long long)chunk * tpw; t < t_end; ++t) {
     const long long m0 = t * kProjTile;
     __syncthreads();
-    for (int i = tid; i < kProjStage; i += 256) {                       // local q <-> s[m0 - 512 + q]
-      const long long g = m0 - kFlen + i;
-      S[pos16(i)] = (g >= 0 && g < N) ? (double)s[g] : 0.0;
-    }
+    proj_stage(s, N, m0, S);
     __syncthreads();
-    const int q0 = kFlen + tid * 16;                                    // this lane's outputs m0 + 16 tid + i, local q0 + i
-    double acc[16], w[16];                                              // slot (q - q0) & 15 holds s at local q
+    double acc[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      acc[i] = 0.0;
-      w[i] = S[pos16(q0 + i)];
-    }
-    for (int kb = 0; kb < kFlen; kb += 16) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int k = kb + u;
-        const double c = Cl[k];                                         // broadcast
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = fma(c, w[(i - u) & 15], acc[i]);    // C[k] s[m - k]
-        w[(15 - u) & 15] = S[pos16(q0 - k - 1)];                        // s[q0 + 15 - k] is done, s[q0 - k - 1] next
-      }
-    }
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0;
+    proj_filter(S, Cl, acc);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const long long m = m0 + tid * 16 + i;
@@ -317,9 +158,6 @@ __global__ void __launch_bounds__(64) sdr_final_kernel(const double* __restrict_
   }
   sdr[row] = rr == 0.0 ? __builtin_inf() : 10.0 * log10(pp / rr);
 }
-
-constexpr int kMaxRows = 1 << 20;
-constexpr long long kMaxLen = 1LL << 40;
 
 }  // namespace
 

@@ -18,8 +18,20 @@ come from the GPU front end (``audio.wav_to_spec``), the estimate from ``audio.s
 Batches of at most ``batch_size`` items are planned over the whole set by length (``streaming.plan_ragged_batches``), the
 network runs each padded batch with every item computed as if alone (``model.forward_ragged``), and loss and SDR are taken
 per item at its own length and averaged over items (``Trainer.evaluate_ragged``).
+
+``--speakers-csv FILE``: several enrolled speakers per mixture.  Every row of FILE is
+``mixed_wav,emb_1,target_wav_1,...,emb_K,target_wav_K`` (paths relative to ``-d``, the same K in every row); the K speakers
+are extracted in one pass (``model.forward_multi``) and scored with the multi-source BSS-eval (``metrics.bss_eval``) by
+``Trainer.evaluate_speakers``:
+
+        Mean Test SDR: ...  Mean Test SIR: ...  Mean Test SAR: ...      (output k against speaker k)
+        Speaker confusion: ...                                            (share of items whose best permutation is not the identity)
+
+Under ``--checkpoints_path`` the four numbers are printed and written per checkpoint; the best checkpoint is the one with
+the largest mean SDR.
 """
 import argparse
+import csv
 import json
 import os
 import shutil
@@ -110,6 +122,92 @@ def eval_batches(c, ds: EvalDataset, device, ragged: bool = False):
         yield emb, target, mixed, seq_len, target_wav, phase
 
 
+def read_speakers_csv(path: str):
+    """The rows of a ``--speakers-csv`` file: ``[(mixed_wav, [(emb_1, target_wav_1), .., (emb_K, target_wav_K)]), ..]``.
+    Empty lines and lines starting with '#' are skipped; every row must have 1 + 2 K fields with the same K >= 1."""
+    rows = []
+    with open(path, newline="") as f:
+        for ln, rec in enumerate(csv.reader(f), 1):
+            rec = [x.strip() for x in rec]
+            if not rec or not any(rec) or rec[0].startswith("#"):
+                continue
+            if len(rec) < 3 or len(rec) % 2 != 1 or not all(rec):
+                raise ValueError(f"{path}:{ln}: expected mixed_wav,emb_1,target_wav_1,...,emb_K,target_wav_K, got {len(rec)} fields")
+            rows.append((rec[0], [(rec[i], rec[i + 1]) for i in range(1, len(rec), 2)]))
+            if len(rows[-1][1]) != len(rows[0][1]):
+                raise ValueError(f"{path}:{ln}: {len(rows[-1][1])} speakers, the rows before have {len(rows[0][1])}")
+    if not rows:
+        raise ValueError(f"{path}: no rows")
+    return rows
+
+
+def speaker_items(rows, root: str, sample_rate: int, load_emb=torch.load, load=load_wav):
+    """(emb [K, E], target_wavs [K, S], mixed_wav [S], names) per row of ``read_speakers_csv``, paths taken relative to root."""
+    for mixed, speakers in rows:
+        emb = torch.stack([load_emb(os.path.join(root, e)).float().reshape(-1) for e, _ in speakers])
+        targets = [load(os.path.join(root, t), sample_rate) for _, t in speakers]
+        yield emb, targets, load(os.path.join(root, mixed), sample_rate), [mixed] + [t for _, t in speakers]
+
+
+def group_speaker_items(items, bs: int):
+    """Host batches of at most ``bs`` items in order: (emb [B, K, E], target_wavs [B, K, S], mixed_wav [B, S]); every waveform
+    of one batch must have the same length."""
+    items = list(items)
+    for lo in range(0, len(items), bs):
+        group = items[lo:lo + bs]
+        lengths = {int(w.shape[0]) for it in group for w in it[1] + [it[2]]}
+        if len(lengths) != 1:
+            desc = ", ".join(f"{os.path.basename(n)} ({w.shape[0]})" for it in group for n, w in zip(it[3], [it[2]] + it[1]))
+            raise ValueError(f"items of one test batch must share a length (test_config.batch_size = {bs}): {desc}")
+        yield (torch.stack([it[0] for it in group]), torch.stack([torch.stack(it[1]) for it in group]),
+               torch.stack([it[2] for it in group]))
+
+
+def speaker_batches(c, rows, root: str, device):
+    """``Trainer.evaluate_speakers``'s batches from the rows of a speakers CSV: (emb, mixed_spec, mixed_phase, target_wavs)."""
+    from . import audio
+    acfg = c.audio[c.audio["backend"]]
+    bs = int(c["test_config"]["batch_size"]) if "test_config" in c else 1
+    for emb, target_wavs, mixed_wav in group_speaker_items(speaker_items(rows, root, int(acfg["sample_rate"])), bs):
+        mixed, phase = audio.wav_to_spec(mixed_wav.to(device), acfg, want_phase=True)
+        yield emb.to(device), mixed, phase, target_wavs
+
+
+def _speakers_main(args, c, tr: Trainer, dev):
+    rows = read_speakers_csv(args.speakers_csv)
+
+    def score(path):
+        tr.load_checkpoint(path)
+        return tr.evaluate_speakers(speaker_batches(c, rows, args.dataset_dir, dev))
+
+    def line(m):
+        return (f"Mean Test SDR: {m['sdr']} Mean Test SIR: {m['sir']} Mean Test SAR: {m['sar']} "
+                f"Speaker confusion: {m['confusion']}")
+
+    if args.checkpoint_path:
+        m = score(args.checkpoint_path)
+        for name, key in (("Mean Test SDR", "sdr"), ("Mean Test SIR", "sir"), ("Mean Test SAR", "sar"), ("Speaker confusion", "confusion")):
+            print(f"{name}:", m[key])
+        return m
+    paths = [p for p in sorted(glob(os.path.join(args.checkpoints_path, "*.pt"))) if os.path.basename(p) != "best_checkpoint.pt"]
+    if not paths:
+        raise FileNotFoundError(f"no *.pt checkpoints in {args.checkpoints_path}")
+    table = []
+    for p in paths:
+        m = score(p)
+        print(f"{p}: {line(m)}", flush=True)
+        table.append({"checkpoint": p, **m})
+    scored = [t for t in table if t["sdr"] == t["sdr"]]
+    if not scored:
+        raise RuntimeError("no checkpoint has a mean SDR: every test item was skipped")
+    best = max(scored, key=lambda t: t["sdr"])
+    print("Best SDR checkpoint is: ", best["checkpoint"], line(best))
+    out = args.json or os.path.join(args.checkpoints_path, "speakers_per_checkpoint.json")
+    with open(out, "w") as f:
+        json.dump({"checkpoints": table, "best_sdr": best}, f, indent=1)
+    return table
+
+
 def build_trainer(c, device) -> Trainer:
     from . import VoiceFilter, VoiceSplit
     if c.model_name == "voicefilter":
@@ -140,12 +238,19 @@ def main(argv=None):
     ap.add_argument("--json", default=None, help="--checkpoints_path: where the per-checkpoint table goes")
     ap.add_argument("--ragged", action="store_true",
                     help="test items may differ in length: ragged batches, loss and SDR per item at its own length")
+    ap.add_argument("--speakers-csv", default=None,
+                    help="several enrolled speakers per mixture: rows mixed_wav,emb_1,target_wav_1,...,emb_K,target_wav_K "
+                         "relative to -d; prints mean SDR / SIR / SAR and the speaker confusion")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("voicesplit_amd.evaluate needs a GPU: the evaluation path has no CPU implementation")
     c = load_config(args.config_path)
-    c.dataset["test_dir"] = args.dataset_dir
     dev = torch.device("cuda", torch.cuda.current_device())
+    if args.speakers_csv:                                   # the CSV names the files: no c.dataset globs
+        if args.ragged:
+            raise ValueError("--speakers-csv scores batches of one length: group the rows by length instead of --ragged")
+        return _speakers_main(args, c, build_trainer(c, dev), dev)
+    c.dataset["test_dir"] = args.dataset_dir
     ds = EvalDataset(c, args.dataset_dir)
     tr = build_trainer(c, dev)
     if args.checkpoint_path:

@@ -461,6 +461,53 @@ class Trainer:
         acc = acc.tolist()
         return (acc[0] / acc[1] if acc[1] > 0 else float("nan")), (acc[2] / acc[3] if acc[3] > 0 else float("nan"))
 
+    @torch.no_grad()
+    def evaluate_speakers(self, batches: Iterable):
+        """Scores the extraction of K enrolled speakers per mixture: ``{"sdr", "sir", "sar", "confusion"}`` over this rank's
+        batches, averaged over ranks.  Batches are ``(emb [B, K, E], mixed [B, T, F], phase [B, T, F], target_wavs [B, K, S])``,
+        S = hop * (T - 1).  Per batch: ``masks = model.forward_multi(mixed, emb)``, one ``audio.spec_to_wav`` over the B * K rows
+        (as ``audio.separate_speakers`` forms them) and one ``metrics.bss_eval`` call with all K x K pairs.
+
+        sdr / sir / sar: the mean, over the scored items' sources, of estimate k against reference k (the pairs' diagonal: did
+        the output enrolled for speaker k deliver speaker k).  confusion: the share of scored items whose best permutation by
+        mean SIR is not the identity (an output that follows another speaker than the one enrolled for it).  Items with
+        ``bss_eval`` status != 0 (a silent row, a failed solve) are skipped, as ``evaluate`` skips them; NaN when none is left."""
+        from . import audio, metrics
+        self.model.eval()
+        acfg = self.c.audio[self.c.audio["backend"]]
+        dev = self.device
+        acc = torch.zeros(6, dtype=torch.float64, device=dev)      # sums of sdr, sir, sar; sources, items scored; items confused
+        for emb, mixed, phase, target_wavs in batches:
+            if emb is None or len(emb) == 0:
+                continue
+            emb, mixed, phase = (t.to(dev) for t in (emb, mixed, phase))
+            ref = target_wavs.to(dev, torch.float32)
+            B, K = emb.shape[0], emb.shape[1]
+            T, F = mixed.shape[1], mixed.shape[2]
+            masks = self.model.forward_multi(mixed, emb)
+
+            def per_speaker(t):                                     # [B, T, F] -> [B*K, T, F], row b*K + k = mixture b
+                return t[:, None].expand(B, K, T, F).reshape(B * K, T, F).contiguous()
+
+            est = audio.spec_to_wav(per_speaker(mixed), per_speaker(phase), acfg, mask=masks.reshape(B * K, T, F).contiguous())
+            _, _, _, perm, status, pairs = metrics.bss_eval(ref, est.view(B, K, -1), compute_permutation=True, return_pairs=True)
+            ok = status == 0
+            diag = torch.diagonal(pairs, dim1=2, dim2=3)            # [B, 3, K]: estimate k against reference k
+            diag = torch.where(ok[:, None, None], diag, torch.zeros_like(diag))
+            ident = torch.arange(K, dtype=perm.dtype, device=dev)
+            confused = ok & (perm != ident).any(dim=1)
+            n_ok = ok.sum().to(torch.float64)
+            acc += torch.cat([diag.sum(dim=(0, 2)), torch.stack([n_ok * K, n_ok, confused.sum().to(torch.float64)])])
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(acc, group=self.group)
+        self.model.train()
+        a = acc.tolist()
+        nan = float("nan")
+        out = {name: (a[i] / a[3] if a[3] > 0 else nan) for i, name in enumerate(("sdr", "sir", "sar"))}
+        out["confusion"] = a[5] / a[4] if a[4] > 0 else nan
+        return out
+
     def _with_decisions(self, batches: Iterable):
         """Yields (batch, have, next_missing) for ``train_step``.  One rank: have = None (decided in the step, no collective).
         Several ranks: the epoch's first two decisions come from ONE blocking MIN-reduce; from then on every rank's "my batch k + 2 is
