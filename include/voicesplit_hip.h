@@ -1001,6 +1001,67 @@ int vs_resample(const vs_resample_dims* dims, const float* bank, const float* x,
 int vs_resample_clips(const vs_resample_dims* dims, const float* bank, const float* in, long long in_total, float* out,
                       long long out_total, const long long* clips_host, const long long* clips, int N, void* stream);
 
+/* =============================================================================================
+ * ABI 11 (additive entries).  Programme loudness on the device: the other half of the reference's scripts/normalise-resample.sh
+ * (`ffmpeg-normalize <file> -ar 16000` per utterance; -ar is vs_resample_clips).  The measure is ITU-R BS.1770-4 integrated
+ * loudness of a MONO signal; the normalisation is ONE LINEAR GAIN per clip with a peak cap, not ffmpeg's `loudnorm` in its dynamic
+ * mode.  The K-weighting constants are libebur128's AS REMEMBERED (at 48 kHz they give the coefficient table of BS.1770 to 9e-16):
+ * RESTATED, NOT COMPARED WITH AN FFMPEG OR LIBEBUR128 RUN (neither is available where this was written).  This text is the contract;
+ * tests/loudness_ref.py restates it in fp64.
+ *
+ * Mono clip x[0 .. n) fp32 at the integer rate fs, 8000 <= fs <= 192000.  All arithmetic below is fp64.
+ * K-weighting: two biquads re-derived per rate by the bilinear transform,
+ *   stage 1 (shelf):     f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *     K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2
+ *     b1 = {(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0},  a1 = {2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0}
+ *   stage 2 (high-pass): f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan(pi f0 / fs), d = 1 + K/Q + K^2
+ *     b2 = {1, -2, 1},  a2 = {2 (K^2 - 1)/d, (1 - K/Q + K^2)/d}
+ * both in transposed direct form II from a zero state s = (s1, s2, s3, s4), per sample:
+ *   u = b1[0] x + s1;  s1 = b1[1] x - a1[0] u + s2;  s2 = b1[2] x - a1[1] u
+ *   w = u + s3;        s3 = -2 u - a2[0] w + s4;      s4 = u - a2[1] w
+ * Blocks: S = (fs + 5) / 10 (integer division) samples per 100 ms sub-block; m = floor(n / S) sub-blocks with energies
+ *   e_k = sum of w^2 over [k S, (k + 1) S); samples from m S on are never counted; blocks j = 0 .. m - 4 have
+ *   z_j = (e_j + e_{j+1} + e_{j+2} + e_{j+3}) / (4 S).
+ * Gates: absolute z_j > 10^((-70 + 0.691) / 10); relative z_j > 0.1 * mean(z over the absolute-gated blocks) (-10 LU);
+ *   lufs = -0.691 + 10 log10(mean(z over the blocks past both gates));
+ *   counts = (number of blocks = max(m - 3, 0), past the absolute gate, past both).
+ *   With m < 4, or with no block past the absolute gate: lufs = -inf, valid = 0; otherwise valid = 1.
+ * Peak: peak = max |x| over all n samples in fp32, exact and order-independent (0 for n = 0).
+ *
+ * The device evaluates the recurrence in segments of S samples (csrc/loudness.hip): the state behind sub-block k is
+ * s(k+1) = step s(k) + p(k), p(k) the state the sub-block leaves from a zero state.  The products and sums of the recurrence are
+ * fused multiply-adds there, so e_k agrees with the serial fp64 filter to rounding (a few 1e-14 dB in lufs), not to the bit.
+ * A clip's results are bit-identical whatever its offset in the buffer, its neighbours, N and the call.
+ *
+ * vs_loudness_plan: host only, no device; -1 and a message for a rate outside 8000 .. 192000.  step[r][c]: component r of the state
+ * after S zero-input samples from the unit state c, built by running the recurrence itself S times (not by matrix powers).  Every
+ * other call checks the dims it is given against a plan of its own.
+ * vs_loudness: clips [N][2] int64 on the device = (at, n), clip i = samples[at : at + n], any alignment, 0 <= n <= 2^30;
+ * clips_host the same values in HOST memory, checked here before anything is launched (-1 and a message for a clip that leaves
+ * [0, total] or is longer than 2^30).  lufs [N] fp64, peak [N] fp32, counts [N][3] int32, valid [N] int32, all on the device.
+ * energy: NULL, or the e_k of all clips, clip i's m_i values from energy[energy_at[i]] on (energy_at [N] int64 on the device; the
+ * regions are the caller's and are not checked).  workspace: 256-byte aligned; vs_loudness_workspace_bytes(dims, total, N) bytes
+ * serve any N clips of one buffer of `total` samples that do not overlap (clips that overlap may need more: a workspace too small
+ * for the table is refused with a message; 0 from the size function is an error).  Nothing outside a clip is read, nothing is
+ * allocated, no environment variable is read; NULL pointers are refused with a message.  Five launches on `stream` for up to 65535
+ * clips (slots, zero-state sweep, scan, energy sweep, gate), two more per further 65535.
+ * vs_scale_clips: x = x * gain[i] (one fp32 multiply) for every sample of clip i, in place; gain [N] fp32 on the device; the table as
+ * above.  Nothing outside a clip is read or written; clips of a table must not overlap (not checked).  16-byte loads and stores where
+ * the alignment allows, single floats at a clip's head and tail.
+ * ============================================================================================= */
+typedef struct vs_loudness_dims {
+  int sample_rate, sub;                  /* sub = S */
+  double b1[3], a1[2], b2[3], a2[2];
+  double step[4][4];                     /* s(k+1) = step s(k) + p(k) */
+} vs_loudness_dims;
+int vs_loudness_plan(int sample_rate, vs_loudness_dims* dims);
+size_t vs_loudness_workspace_bytes(const vs_loudness_dims* dims, long long total, int N);
+int vs_loudness(const vs_loudness_dims* dims, const float* samples, long long total, const long long* clips_host,
+                const long long* clips, int N, double* lufs, float* peak, int* counts, int* valid, double* energy,
+                const long long* energy_at, void* workspace, size_t workspace_bytes, void* stream);
+int vs_scale_clips(float* samples, long long total, const long long* clips_host, const long long* clips, const float* gain, int N,
+                   void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

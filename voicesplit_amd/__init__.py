@@ -12,6 +12,9 @@ Public surface (mirrors the reference):
   d-vector (notebooks/GE2E-Seungwonpark-ExtractSpeakerEmbedding-...py), ``voicesplit_amd/speaker.py``.
 * ``resample.Resampler`` / ``resample.StreamingResampler`` / ``audio.resample``: sample-rate conversion on the device, the
   reference's ``librosa.load(path, sr=sample_rate)`` (``voicesplit_amd/resample.py``).
+* ``loudness.LoudnessMeter`` / ``loudness.integrated_loudness`` / ``loudness.normalize``: ITU-R BS.1770-4 integrated loudness and a
+  linear gain with a peak cap on the device, the loudness half of the reference's ``scripts/normalise-resample.sh``
+  (``voicesplit_amd/loudness.py``; not ffmpeg's dynamic ``loudnorm``).
 * ``ops``: stage-level entry points over the C ABI of ``libvoicesplit_hip.so``.
 
 The compute path is the HIP library only; there is no PyTorch/CPU fallback.

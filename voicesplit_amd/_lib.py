@@ -6,7 +6,7 @@ loaded so that both resolve the same ``libamdhip64`` already mapped into the pro
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvoicesplit_hip.so")
@@ -65,6 +65,11 @@ class VsSpeakerParams(Structure):
 
 class VsResampleDims(Structure):
     _fields_ = [(n, c_int) for n in ("sr_in", "sr_out", "L", "M", "H", "T", "tile_periods", "lds_bytes")] + [("bank_bytes", c_size_t)]
+
+
+class VsLoudnessDims(Structure):
+    _fields_ = [("sample_rate", c_int), ("sub", c_int), ("b1", c_double * 3), ("a1", c_double * 2), ("b2", c_double * 3),
+                ("a2", c_double * 2), ("step", (c_double * 4) * 4)]
 
 
 class VsConvLayerGrad(Structure):
@@ -245,6 +250,11 @@ SIGNATURES = {
     "vs_resample": (c_int, [POINTER(VsResampleDims), _P, _P, c_longlong, c_longlong, c_longlong, c_longlong, _P, c_longlong, c_longlong,
                             c_longlong, c_int, _P]),
     "vs_resample_clips": (c_int, [POINTER(VsResampleDims), _P, _P, c_longlong, _P, c_longlong, _P, _P, c_int, _P]),
+    # programme loudness
+    "vs_loudness_plan": (c_int, [c_int, POINTER(VsLoudnessDims)]),
+    "vs_loudness_workspace_bytes": (c_size_t, [POINTER(VsLoudnessDims), c_longlong, c_int]),
+    "vs_loudness": (c_int, [POINTER(VsLoudnessDims), _P, c_longlong, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "vs_scale_clips": (c_int, [_P, c_longlong, _P, _P, _P, c_int, _P]),
 }
 
 _lib = None

@@ -131,14 +131,23 @@ def resample(wav: torch.Tensor, sr_in: int, sr_out: int) -> torch.Tensor:
     return resampler(sr_in, sr_out, wav.device)(wav)
 
 
-def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg, refine_iters: int = 0, sample_rate: int = None) -> torch.Tensor:
+def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg, refine_iters: int = 0, sample_rate: int = None,
+             loudness: float = None) -> torch.Tensor:
     """Target-speaker waveform for a batch of 3 s mixtures, all on the device:
     wav [B, hop*(T-1)], dvec [B, emb_dim] -> est_wav [B, hop*(T-1)]   (test.py's loop body).  refine_iters > 0: that many
     Griffin-Lim rounds on the masked spectrogram, started from the mixture's phase (``griffin_lim`` with power 1).
     sample_rate: the rate of ``wav`` when it is not ``audio_cfg["sample_rate"]`` (16000 when the config names none); wav is then
     [B, n] for any n: converted to the configured rate, padded with zeros to a multiple of hop_length, separated, converted back
-    and cut to n samples."""
+    and cut to n samples.
+    loudness: None, or the level in LUFS of the corpus the network was trained on: every row is first brought there
+    (``loudness.normalize_clips_`` at the rate of ``wav``: BS.1770 integrated loudness, one linear gain g under a -2 dB peak cap) and
+    the estimate is returned at the input's own level, multiplied by fp32(1 / g).  Rows without a loudness keep g = 1."""
     own = int(audio_cfg.get("sample_rate", 16000))
+    if loudness is not None:
+        from .loudness import _rows_table, normalize_clips_
+        x = wav.contiguous().clone()
+        gain = normalize_clips_(*_rows_table(x), int(sample_rate) if sample_rate is not None else own, float(loudness))[1]
+        return separate(model, x, dvec, audio_cfg, refine_iters, sample_rate) * (1.0 / gain)[:, None]
     if sample_rate is not None and int(sample_rate) != own:
         n, hop = wav.shape[1], int(audio_cfg["hop_length"])
         x = resample(wav, int(sample_rate), own)

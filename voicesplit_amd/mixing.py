@@ -39,9 +39,13 @@ class ClipPool:
     construction by ``vs_trim_bounds`` and copied to the host once: ``bounds`` [N, 2] int32 = ``librosa.effects.trim(y, top_db=20)``'s
     (start, end) and ``peak`` [N] = max |y| over the trimmed region."""
 
-    def __init__(self, waveforms: Sequence[torch.Tensor], device="cuda:0", trim: bool = True):
+    def __init__(self, waveforms: Sequence[torch.Tensor], device="cuda:0", trim: bool = True, normalize: Optional[float] = None,
+                 sample_rate: int = 16000, peak_db: Optional[float] = -2.0):
         """trim=False (a pool of noise recordings, which are used whole): no ``vs_trim_bounds`` pass and no minimum length;
-        ``bounds`` is (0, n) for every clip and ``peak`` is None."""
+        ``bounds`` is (0, n) for every clip and ``peak`` is None.
+        normalize: None, or the target in LUFS: every clip (at ``sample_rate``) is brought to it by ``loudness.normalize_clips_``
+        (BS.1770 integrated loudness, one linear gain, peak cap ``peak_db``) before the trim pass, so ``bounds``, ``peak`` and
+        ``range`` are those of the normalised clips; ``lufs`` [N] fp64 (before the gain) and ``gain`` [N] fp32 are kept on the host."""
         device = torch.device(device)
         if device.type != "cuda":
             raise _lib.VoiceSplitHipError(f"ClipPool on {device}: this path only runs on an MI355X (HIP) device; there is no CPU fallback")
@@ -62,16 +66,19 @@ class ClipPool:
         for o, w in zip(self.offsets.tolist(), waveforms):
             self.flat[o:o + w.numel()].copy_(w)
         self.offsets_dev = self.offsets.to(device)
+        self._normalize(normalize, sample_rate, peak_db)
         self._trim() if trim else self._whole()
 
     @classmethod
-    def from_files(cls, paths: Sequence[str], sample_rate: int, device="cuda:0", resample: bool = False, trim: bool = True) -> "ClipPool":
+    def from_files(cls, paths: Sequence[str], sample_rate: int, device="cuda:0", resample: bool = False, trim: bool = True,
+                   normalize: Optional[float] = None, peak_db: Optional[float] = -2.0) -> "ClipPool":
         """resample=False: every file must be at ``sample_rate`` (``load_wav`` raises otherwise).  resample=True: what
         ``librosa.load(path, sr=sample_rate)`` does -- the files are grouped by their own rate, every off-rate group is uploaded as it
-        is and converted by one ``vs_resample_clips`` call straight into the pool's flat buffer, files at ``sample_rate`` are copied."""
+        is and converted by one ``vs_resample_clips`` call straight into the pool's flat buffer, files at ``sample_rate`` are copied.
+        normalize: None, or the target in LUFS (see ``__init__``); the gain is applied after the conversion and before the trim pass."""
         from .trainer import load_wav, load_wav_native
         if not resample:
-            return cls([load_wav(p, sample_rate) for p in paths], device, trim)
+            return cls([load_wav(p, sample_rate) for p in paths], device, trim, normalize, sample_rate, peak_db)
         from .resample import Resampler, out_len, plan
         loaded = [load_wav_native(p) for p in paths]
         plans = {sr: plan(sr, sample_rate) for sr in sorted({sr for _, sr in loaded})}
@@ -92,8 +99,19 @@ class ClipPool:
             for o, k in zip(table[:, 0].tolist(), group):
                 staged[o:o + loaded[k][0].numel()].copy_(loaded[k][0])
             Resampler(sr, sample_rate, self.device).clips_into(staged, self.flat, table)
+        self._normalize(normalize, sample_rate, peak_db)
         self._trim() if trim else self._whole()
         return self
+
+    def _normalize(self, target: Optional[float], sample_rate: int, peak_db: Optional[float]) -> None:
+        """normalize=None leaves the pool as it is (``lufs`` and ``gain`` are None)."""
+        self.lufs = self.gain = None
+        if target is None:
+            return
+        from .loudness import normalize_clips_
+        table = torch.stack((self.offsets[:-1], self.offsets[1:] - self.offsets[:-1]), dim=1)
+        lufs, gain = normalize_clips_(self.flat, table, int(sample_rate), float(target), peak_db)
+        self.lufs, self.gain = lufs.cpu(), gain.cpu()
 
     def _layout(self, sizes: Sequence[int], device, trim: bool = True) -> None:
         """offsets / total / an uninitialised ``flat`` for clips of ``sizes`` samples."""
@@ -119,6 +137,7 @@ class ClipPool:
         (min, max) of every trimmed region, what ``ClipPool.range`` computes on the device (the overlay planner reads it)."""
         self = cls.__new__(cls)
         self.device, self.flat, self.offsets_dev = None, None, None
+        self.lufs = self.gain = None
         self.offsets = torch.zeros(len(lengths) + 1, dtype=torch.int64)
         self.offsets[1:] = torch.tensor(list(lengths), dtype=torch.int64).cumsum(0)
         self.total = int(self.offsets[-1])
@@ -907,6 +926,9 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--resample", action="store_true", help="convert files at another rate to the configured one on the device "
                     "(librosa.load(path, sr=sample_rate)); without it such a file is an error")
+    ap.add_argument("--normalize", nargs="?", type=float, const=-23.0, default=None, metavar="LUFS",
+                    help="bring every utterance to this BS.1770 integrated loudness on the device first (default target -23; one "
+                    "linear gain with a -2 dB peak cap, not ffmpeg's dynamic loudnorm); the noise recordings are left as they are")
     ap.add_argument("--no-overlay", action="store_true", help="preprocess_by_csv_without_voice_overlay.py: the speakers take turns "
                     "over two noise recordings, four items (%%06d_1 .. _4) per triplet; needs --noise-csv")
     ap.add_argument("--noise-csv", default=None, help="--no-overlay: one noise file per line, relative to the dataset root")
@@ -932,7 +954,7 @@ def main(argv=None):
         written = 0
         if triplets and args.no_overlay:
             sr = int(audio_cfg["sample_rate"])
-            pool = ClipPool.from_files(paths, sr, args.device, resample=args.resample)
+            pool = ClipPool.from_files(paths, sr, args.device, resample=args.resample, normalize=args.normalize)
             noise_pool = ClipPool.from_files(read_noise_csv(args.noise_csv, args.dataset_root_dir), sr, args.device, resample=args.resample,
                                              trim=False)
             written, dropped = write_overlay_dataset(pool, noise_pool, triplets, numbers, out, audio_cfg, form, args.batch, encoder, args.seed)
@@ -940,7 +962,7 @@ def main(argv=None):
                   f"{skipped} skipped for a missing file")
             continue
         if triplets:
-            pool = ClipPool.from_files(paths, int(audio_cfg["sample_rate"]), args.device, resample=args.resample)
+            pool = ClipPool.from_files(paths, int(audio_cfg["sample_rate"]), args.device, resample=args.resample, normalize=args.normalize)
             written = write_dataset(pool, triplets, numbers, out, audio_cfg, c.audio["audio_len"], form, args.batch, encoder)
         print(f"{name}: {written} triplets written to {out}, {len(triplets) - written} too short or silent, "
               f"{skipped} skipped for a missing file")

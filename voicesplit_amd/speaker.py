@@ -15,7 +15,7 @@ import argparse
 import ctypes
 import glob
 import os
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -291,20 +291,28 @@ def embed_directory(encoder, data_dir: str, audio_cfg, batch: int = 64, device="
     return good
 
 
-def resampling_loader(device="cuda:0"):
+def resampling_loader(device="cuda:0", resample: bool = True, normalize: Optional[float] = None):
     """A ``load_wav(path, sample_rate)`` for ``embed_directory`` that accepts a file at any rate and converts it on the device
-    (``librosa.load(path, sr=sample_rate)``); one ``resample.Resampler`` per source rate."""
+    (``librosa.load(path, sr=sample_rate)``); one ``resample.Resampler`` per source rate.  resample=False: a file at another rate is
+    an error, as with ``trainer.load_wav``.  normalize: None, or the target in LUFS the clip is brought to on the device
+    (``loudness.normalize``: one linear gain with a peak cap) behind the conversion."""
     from .resample import Resampler
-    from .trainer import load_wav_native
+    from .trainer import load_wav as load_at_rate, load_wav_native
     resamplers = {}
 
     def load(path, sample_rate):
-        wav, native = load_wav_native(path)
-        if native == sample_rate:
-            return wav
-        if native not in resamplers:
-            resamplers[native] = Resampler(native, sample_rate, device)
-        return resamplers[native](wav.to(device))
+        if not resample:
+            wav = load_at_rate(path, sample_rate)
+        else:
+            wav, native = load_wav_native(path)
+            if native != sample_rate:
+                if native not in resamplers:
+                    resamplers[native] = Resampler(native, sample_rate, device)
+                wav = resamplers[native](wav.to(device))
+        if normalize is not None and wav.numel():
+            from .loudness import normalize as to_level
+            wav = to_level(wav.to(device), sample_rate, float(normalize))
+        return wav
     return load
 
 
@@ -318,15 +326,18 @@ def main(argv=None):
     ap.add_argument("--root", default="..", help="directory the paths inside *-ref_emb.wav are relative to")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--resample", action="store_true", help="convert reference clips at another rate to the configured one on the device")
+    ap.add_argument("--normalize", nargs="?", type=float, const=-23.0, default=None, metavar="LUFS",
+                    help="bring every reference clip to this BS.1770 integrated loudness on the device first (default target -23; one "
+                    "linear gain with a -2 dB peak cap, not ffmpeg's dynamic loudnorm)")
     args = ap.parse_args(argv)
     c = load_config(args.config) if args.config else default_config()
     audio_cfg = c.audio[c.audio["backend"]]
     enc = SpeakerEncoder(num_mels=int(audio_cfg.get("num_mels", 40)))
     enc.load_state_dict(torch.load(args.checkpoint, map_location="cpu"), strict=True)
     enc = enc.eval().to(args.device)
+    loader = resampling_loader(args.device, args.resample, args.normalize) if args.resample or args.normalize is not None else None
     for d in args.data_dir:
-        n = embed_directory(enc, d, audio_cfg, batch=args.batch, device=args.device, root=args.root,
-                            load_wav=resampling_loader(args.device) if args.resample else None)
+        n = embed_directory(enc, d, audio_cfg, batch=args.batch, device=args.device, root=args.root, load_wav=loader)
         print(f"{d}: {n} embeddings written")
 
 

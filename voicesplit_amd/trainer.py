@@ -763,7 +763,8 @@ def _mixture_batches(args, c, acfg, b, rank, world, dev):
     paths, triplets, numbers, skipped = mixing.read_triplet_csv(args.mix_csv, args.mix_root, args.librispeech)
     if not triplets:
         raise ValueError(f"{args.mix_csv}: no triplet with all three files under {args.mix_root}")
-    pool = mixing.ClipPool.from_files(paths, int(acfg["sample_rate"]), dev, resample=bool(getattr(args, "resample", False)))
+    pool = mixing.ClipPool.from_files(paths, int(acfg["sample_rate"]), dev, resample=bool(getattr(args, "resample", False)),
+                                      normalize=getattr(args, "normalize", None))
     if getattr(args, "no_overlay", False):
         return _overlay_batches(args, c, acfg, b, rank, world, dev, pool, triplets, numbers)
     L = mixing.samples_for(acfg, c.audio["audio_len"])
@@ -849,6 +850,9 @@ def main(argv=None):
     ap.add_argument("--mix-root", default=".", help="directory the CSV's names are relative to")
     ap.add_argument("--librispeech", action="store_true", help="the CSV holds LibriSpeech utterance ids (preprocess_by_csv.py -l)")
     ap.add_argument("--resample", action="store_true", help="--mix-csv: convert files at another rate to the configured one on the device")
+    ap.add_argument("--normalize", nargs="?", type=float, const=-23.0, default=None, metavar="LUFS",
+                    help="--mix-csv: bring every utterance to this BS.1770 integrated loudness on the device first (default target -23; "
+                    "one linear gain with a -2 dB peak cap, not ffmpeg's dynamic loudnorm); noise recordings are left as they are")
     ap.add_argument("--mix-crop", choices=("head", "random"), default="head", help="head: the reference's [:audio_len]; random: a fresh crop every epoch")
     ap.add_argument("--no-overlay", action="store_true", help="--mix-csv with --noise-csv: the speakers take turns over two noise "
                     "recordings, four items per triplet (preprocess_by_csv_without_voice_overlay.py)")
