@@ -1062,6 +1062,58 @@ int vs_loudness(const vs_loudness_dims* dims, const float* samples, long long to
 int vs_scale_clips(float* samples, long long total, const long long* clips_host, const long long* clips, const float* gain, int N,
                    void* stream);
 
+/* =============================================================================================
+ * ABI 11 (additive entries).  Speech intelligibility on the device: STOI (Taal, Hendriks, Heusdens, Jensen 2011) and its extended
+ * form ESTOI (Jensen, Taal 2016), the scores reported beside the SDR.  The algorithm is pystoi's AS REMEMBERED: RESTATED, NOT
+ * COMPARED WITH A PYSTOI RUN (pystoi is not available where this was written), so parity with pystoi's own numbers is unpinned; in
+ * particular pystoi resamples to 10 kHz with an Octave-style filter and this project uses vs_resample.  This text is the contract;
+ * tests/stoi_ref.py restates it in fp64.
+ *
+ * Both signals x (reference) and y (estimate) are fp32 at fs = 10000 Hz and share a length n.  Every sum and product below is fp64.
+ * Constants: frame W = 256, hop 128, NFFT = 512, J = 15 bands, segment N = 30 frames, DYN = 40 dB, clip factor 1 + 10^(15/20),
+ *   EPS = 2^-52, window w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), i = 0 .. 255 (hanning(258) without its two zeros).
+ * Frames: F = (n - 256) / 128 + 1 (integer division) for n >= 256, else 0; frame f = samples [128 f, 128 f + 256).
+ * Silent-frame removal, decided by x alone: e_f = 20 log10(sqrt(sum (w x_f)^2) + EPS); frame f is kept iff max_f(e) - 40 - e_f < 0;
+ *   q = 0 .. Mk - 1 indexes the kept frames in order.  Both signals are rebuilt by overlap-adding their own windowed kept frames at
+ *   128 q (length (Mk - 1) 128 + 256).
+ * Band envelopes: the rebuilt signals are framed again with the same W, hop and w (exactly Mk frames), every frame zero-padded to 512
+ *   samples, P[k] = |DFT_512|^2; band j sums P[k] over lo_j <= k < hi_j, the edges being the bins of the 10000 / 512 Hz grid nearest
+ *   to 150 * 2^((2 j -+ 1) / 6) Hz: (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109)
+ *   (109,138) (138,174) (174,219); X[j][q] = sqrt(band sum) of x, Y[j][q] of y.
+ * Segments: m = 30 .. Mk, the blocks X[:, m - 30 : m] and Y[:, m - 30 : m]; M = Mk - 29 of them.
+ * STOI: per band row, c = |x| / (|y| + EPS), y' = min(c y, x (1 + 10^0.75)); the row means of x and y' are subtracted, each is
+ *   divided by (its norm + EPS); d = sum x y' / (J M).
+ * ESTOI: both blocks: subtract the row mean and divide by (row norm + EPS), then subtract the column mean and divide by (column norm
+ *   + EPS); d = sum x y / (N M).
+ * status 0 = ok; 1 = Mk < 30 (pystoi warns and returns 1e-5): d = 1e-5 exactly.
+ * Every reduction has a fixed order (csrc/stoi.hip lists them); a clip's results are bit-identical whatever its offset in the
+ * buffers, its neighbours, R and the call.  The device's sums are ordered differently from the restatement's and its products may be
+ * fused, so d agrees with it to rounding, not to the bit; the keep mask is a threshold, exact unless a frame sits on it.
+ *
+ * vs_stoi_plan: host only, no device: the constants above and the band edges, computed (first nearest bin).  Every other call checks
+ * the dims it is given against a plan of its own.
+ * vs_stoi: ref and est are flat buffers of `total` samples; clips [R][2] int64 on the device = (at, n): pair i is ref[at : at + n]
+ * and est[at : at + n], any alignment, 0 <= n <= 2^24; clips_host the same values in HOST memory, checked here before anything is
+ * launched (-1 and a message for a clip that leaves [0, total] or is longer than 2^24).  extended: 0 = STOI, 1 = ESTOI.
+ * d [R] fp64, frames [R][2] int32 = (F, Mk), status [R] int32, all on the device.  tob: NULL, or the envelopes of all clips, clip i's
+ * X then Y as [2][15][Mk_i] from tob[tob_at[i]] on (tob_at [R] int64 on the device; 30 F_i values are always enough; the regions are
+ * the caller's and are not checked).  workspace: 256-byte aligned; vs_stoi_workspace_bytes(dims, total, R) bytes serve any R clips of
+ * buffers of `total` samples that do not overlap (clips that overlap may need more: a workspace too small for the table is refused
+ * with a message; 0 from the size function is an error).  Nothing outside a clip is read, nothing is allocated, no environment
+ * variable is read; NULL pointers are refused with a message.  At most six launches on `stream` for any R (frame slots, frame
+ * energies, gate and compaction, band envelopes, segment correlations, fold); the launches without work for the table are left out.
+ * ============================================================================================= */
+typedef struct vs_stoi_dims {
+  int frame, hop, nfft, bands, seg;
+  int lo[15], hi[15];                    /* band j = bins lo[j] .. hi[j] - 1 */
+  double clip, dyn_db;
+} vs_stoi_dims;
+int vs_stoi_plan(vs_stoi_dims* dims);
+size_t vs_stoi_workspace_bytes(const vs_stoi_dims* dims, long long total, int R);
+int vs_stoi(const vs_stoi_dims* dims, const float* ref, const float* est, long long total, const long long* clips_host,
+            const long long* clips, int R, int extended, double* d, int* frames, int* status, double* tob, const long long* tob_at,
+            void* workspace, size_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -15,6 +15,8 @@ Public surface (mirrors the reference):
 * ``loudness.LoudnessMeter`` / ``loudness.integrated_loudness`` / ``loudness.normalize``: ITU-R BS.1770-4 integrated loudness and a
   linear gain with a peak cap on the device, the loudness half of the reference's ``scripts/normalise-resample.sh``
   (``voicesplit_amd/loudness.py``; not ffmpeg's dynamic ``loudnorm``).
+* ``metrics.bss_sdr`` / ``metrics.bss_eval`` / ``metrics.stoi``: the evaluation scores on the device: BSS-eval SDR, SIR, SAR and
+  the intelligibility scores STOI / ESTOI (``voicesplit_amd/metrics.py``).
 * ``ops``: stage-level entry points over the C ABI of ``libvoicesplit_hip.so``.
 
 The compute path is the HIP library only; there is no PyTorch/CPU fallback.

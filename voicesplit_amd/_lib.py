@@ -72,6 +72,11 @@ class VsLoudnessDims(Structure):
                 ("a2", c_double * 2), ("step", (c_double * 4) * 4)]
 
 
+class VsStoiDims(Structure):
+    _fields_ = [(n, c_int) for n in ("frame", "hop", "nfft", "bands", "seg")] + [("lo", c_int * 15), ("hi", c_int * 15),
+                                                                                 ("clip", c_double), ("dyn_db", c_double)]
+
+
 class VsConvLayerGrad(Structure):
     _fields_ = [(n, c_void_p) for n in ("weight", "bias", "bn_weight", "bn_bias")]
 
@@ -255,6 +260,10 @@ SIGNATURES = {
     "vs_loudness_workspace_bytes": (c_size_t, [POINTER(VsLoudnessDims), c_longlong, c_int]),
     "vs_loudness": (c_int, [POINTER(VsLoudnessDims), _P, c_longlong, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "vs_scale_clips": (c_int, [_P, c_longlong, _P, _P, _P, c_int, _P]),
+    # speech intelligibility
+    "vs_stoi_plan": (c_int, [POINTER(VsStoiDims)]),
+    "vs_stoi_workspace_bytes": (c_size_t, [POINTER(VsStoiDims), c_longlong, c_int]),
+    "vs_stoi": (c_int, [POINTER(VsStoiDims), _P, _P, c_longlong, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -29,6 +29,15 @@ are extracted in one pass (``model.forward_multi``) and scored with the multi-so
 
 Under ``--checkpoints_path`` the four numbers are printed and written per checkpoint; the best checkpoint is the one with
 the largest mean SDR.
+
+``--stoi``: the intelligibility scores beside the distortion ones (``Trainer.evaluate_intelligibility``, or
+``Trainer.evaluate_speakers(stoi=True)`` with ``--speakers-csv``; ``metrics.stoi`` -- restated, not compared with a pystoi run):
+
+        Mean Test STOI: ...
+        Mean Test ESTOI: ...
+
+after the lines above, and the fields ``mean_stoi`` / ``mean_estoi`` (``stoi`` / ``estoi`` with ``--speakers-csv``) in the ``--json``
+table.  Without the flag nothing changes.
 """
 import argparse
 import csv
@@ -178,16 +187,22 @@ def _speakers_main(args, c, tr: Trainer, dev):
 
     def score(path):
         tr.load_checkpoint(path)
+        if args.stoi:
+            return tr.evaluate_speakers(speaker_batches(c, rows, args.dataset_dir, dev), stoi=True)
         return tr.evaluate_speakers(speaker_batches(c, rows, args.dataset_dir, dev))
 
     def line(m):
-        return (f"Mean Test SDR: {m['sdr']} Mean Test SIR: {m['sir']} Mean Test SAR: {m['sar']} "
+        text = (f"Mean Test SDR: {m['sdr']} Mean Test SIR: {m['sir']} Mean Test SAR: {m['sar']} "
                 f"Speaker confusion: {m['confusion']}")
+        return text + (f" Mean Test STOI: {m['stoi']} Mean Test ESTOI: {m['estoi']}" if args.stoi else "")
 
     if args.checkpoint_path:
         m = score(args.checkpoint_path)
         for name, key in (("Mean Test SDR", "sdr"), ("Mean Test SIR", "sir"), ("Mean Test SAR", "sar"), ("Speaker confusion", "confusion")):
             print(f"{name}:", m[key])
+        if args.stoi:
+            print("Mean Test STOI:", m["stoi"])
+            print("Mean Test ESTOI:", m["estoi"])
         return m
     paths = [p for p in sorted(glob(os.path.join(args.checkpoints_path, "*.pt"))) if os.path.basename(p) != "best_checkpoint.pt"]
     if not paths:
@@ -227,6 +242,11 @@ def score_checkpoint(tr: Trainer, path: str, ds: EvalDataset, device, ragged: bo
     return tr.evaluate(eval_batches(tr.c, ds, device))
 
 
+def score_intelligibility(tr: Trainer, ds: EvalDataset, device, ragged: bool = False):
+    """``Trainer.evaluate_intelligibility`` of the checkpoint ``tr`` holds, over the batches ``score_checkpoint`` scores."""
+    return tr.evaluate_intelligibility(eval_batches(tr.c, ds, device, ragged=ragged), ragged=ragged)
+
+
 def main(argv=None):
     from . import load_config
     ap = argparse.ArgumentParser(description="Mean test loss and SDR of VoiceSplit checkpoints (test.py / test_all_checkpoints.py)")
@@ -241,6 +261,8 @@ def main(argv=None):
     ap.add_argument("--speakers-csv", default=None,
                     help="several enrolled speakers per mixture: rows mixed_wav,emb_1,target_wav_1,...,emb_K,target_wav_K "
                          "relative to -d; prints mean SDR / SIR / SAR and the speaker confusion")
+    ap.add_argument("--stoi", action="store_true",
+                    help="also print the mean STOI and ESTOI (intelligibility at 10 kHz) and add them to the --json table")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("voicesplit_amd.evaluate needs a GPU: the evaluation path has no CPU implementation")
@@ -257,6 +279,11 @@ def main(argv=None):
         mean_loss, mean_sdr = score_checkpoint(tr, args.checkpoint_path, ds, dev, ragged=args.ragged)
         print("Mean Test Loss:", mean_loss)
         print("Mean Test SDR:", mean_sdr)
+        if args.stoi:
+            m = score_intelligibility(tr, ds, dev, ragged=args.ragged)
+            print("Mean Test STOI:", m["stoi"])
+            print("Mean Test ESTOI:", m["estoi"])
+            return mean_loss, mean_sdr, m["stoi"], m["estoi"]
         return mean_loss, mean_sdr
     paths = [p for p in sorted(glob(os.path.join(args.checkpoints_path, "*.pt"))) if os.path.basename(p) != "best_checkpoint.pt"]
     if not paths:
@@ -264,8 +291,14 @@ def main(argv=None):
     table = []
     for p in paths:
         mean_loss, mean_sdr = score_checkpoint(tr, p, ds, dev, ragged=args.ragged)
-        print(f"{p}: Mean Test Loss: {mean_loss} Mean Test SDR: {mean_sdr}", flush=True)
-        table.append({"checkpoint": p, "mean_sdr": mean_sdr, "mean_loss": mean_loss})
+        row = {"checkpoint": p, "mean_sdr": mean_sdr, "mean_loss": mean_loss}
+        more = ""
+        if args.stoi:
+            m = score_intelligibility(tr, ds, dev, ragged=args.ragged)
+            row.update(mean_stoi=m["stoi"], mean_estoi=m["estoi"])
+            more = f" Mean Test STOI: {m['stoi']} Mean Test ESTOI: {m['estoi']}"
+        print(f"{p}: Mean Test Loss: {mean_loss} Mean Test SDR: {mean_sdr}{more}", flush=True)
+        table.append(row)
     scored = [t for t in table if t["mean_sdr"] == t["mean_sdr"]]          # NaN: no item of the set could be scored
     if not scored:
         raise RuntimeError("no checkpoint has a mean SDR: every test item was skipped")

@@ -462,7 +462,61 @@ class Trainer:
         return (acc[0] / acc[1] if acc[1] > 0 else float("nan")), (acc[2] / acc[3] if acc[3] > 0 else float("nan"))
 
     @torch.no_grad()
-    def evaluate_speakers(self, batches: Iterable):
+    def evaluate_intelligibility(self, batches: Iterable, ragged: bool = False):
+        """``{"stoi", "estoi", "scored", "skipped"}`` over this rank's test batches, averaged over ranks as ``evaluate`` averages
+        (sums and counts are reduced, then divided): the mean STOI and ESTOI (``metrics.stoi_pair`` at the configured sample rate)
+        of the estimate ``evaluate`` scores by SDR against the target waveform.  Batches are ``evaluate``'s tuples, or with
+        ``ragged`` those of ``evaluate_ragged``: every item is then scored at its own length, the estimates of a batch padded
+        into one call with ``lengths``.  Rows with status 1 (fewer than 30 frames left once the silent frames of the target are
+        removed) are skipped and counted in ``skipped``; NaN means when none is scored."""
+        from . import audio, metrics
+        self.model.eval()
+        acfg = self.c.audio[self.c.audio["backend"]]
+        sr = int(acfg["sample_rate"])
+        dev = self.device
+        acc = torch.zeros(4, dtype=torch.float64, device=dev)      # sum of STOI, of ESTOI; rows scored, skipped
+        for batch in batches:
+            emb = batch[0]
+            if emb is None or len(emb) == 0:
+                continue
+            lengths = None
+            if ragged:
+                emb, _target, mixed, _seq_len, target_wavs, phase, frames = batch
+                emb, mixed, phase = (t.to(dev) for t in (emb, mixed, phase))
+                mask = self.model.forward_ragged(mixed, emb, frames)
+                ests = [audio.spec_to_wav(mixed[b:b + 1, :n], phase[b:b + 1, :n], acfg, mask=mask[b:b + 1, :n])[0]
+                        for b, n in enumerate(int(f) for f in frames)]
+                lengths = [int(e.numel()) for e in ests]
+                est_wav = torch.zeros(len(ests), max(lengths), dtype=torch.float32, device=dev)
+                ref_wav = torch.zeros_like(est_wav)
+                for b, (e, t) in enumerate(zip(ests, target_wavs)):
+                    if t.numel() != e.numel():
+                        raise ValueError(f"item {b}: the target has {t.numel()} samples, the estimate {e.numel()}")
+                    est_wav[b, :lengths[b]] = e
+                    ref_wav[b, :lengths[b]] = t.to(dev, torch.float32)
+            else:
+                emb, _target, mixed, _seq_len, target_wav, phase = batch
+                if target_wav is None:
+                    raise ValueError("evaluate_intelligibility needs the target waveform (5th element of the batch)")
+                emb, mixed, phase = (t.to(dev) for t in (emb, mixed, phase))
+                est_wav = audio.spec_to_wav(mixed, phase, acfg, mask=self.model(mixed, emb))
+                ref_wav = target_wav.to(dev, torch.float32)
+            d, e, status = metrics.stoi_pair(ref_wav, est_wav, sr, lengths=lengths)
+            ok = status == 0
+            zero = torch.zeros_like(d)
+            n_ok = ok.sum().to(torch.float64)
+            acc += torch.stack([torch.where(ok, d, zero).sum(), torch.where(ok, e, zero).sum(), n_ok, ok.numel() - n_ok])
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(acc, group=self.group)
+        self.model.train()
+        a = acc.tolist()
+        nan = float("nan")
+        return {"stoi": a[0] / a[2] if a[2] > 0 else nan, "estoi": a[1] / a[2] if a[2] > 0 else nan,
+                "scored": int(a[2]), "skipped": int(a[3])}
+
+    @torch.no_grad()
+    def evaluate_speakers(self, batches: Iterable, stoi: bool = False):
         """Scores the extraction of K enrolled speakers per mixture: ``{"sdr", "sir", "sar", "confusion"}`` over this rank's
         batches, averaged over ranks.  Batches are ``(emb [B, K, E], mixed [B, T, F], phase [B, T, F], target_wavs [B, K, S])``,
         S = hop * (T - 1).  Per batch: ``masks = model.forward_multi(mixed, emb)``, one ``audio.spec_to_wav`` over the B * K rows
@@ -471,12 +525,16 @@ class Trainer:
         sdr / sir / sar: the mean, over the scored items' sources, of estimate k against reference k (the pairs' diagonal: did
         the output enrolled for speaker k deliver speaker k).  confusion: the share of scored items whose best permutation by
         mean SIR is not the identity (an output that follows another speaker than the one enrolled for it).  Items with
-        ``bss_eval`` status != 0 (a silent row, a failed solve) are skipped, as ``evaluate`` skips them; NaN when none is left."""
+        ``bss_eval`` status != 0 (a silent row, a failed solve) are skipped, as ``evaluate`` skips them; NaN when none is left.
+
+        ``stoi``: two more keys, ``"stoi"`` and ``"estoi"``: the mean intelligibility (``metrics.stoi_pair``) of output k against
+        speaker k over the rows it can score (status 0), whatever ``bss_eval`` said of the item."""
         from . import audio, metrics
         self.model.eval()
         acfg = self.c.audio[self.c.audio["backend"]]
         dev = self.device
         acc = torch.zeros(6, dtype=torch.float64, device=dev)      # sums of sdr, sir, sar; sources, items scored; items confused
+        acc_i = torch.zeros(3, dtype=torch.float64, device=dev)    # sums of STOI, ESTOI; rows scored
         for emb, mixed, phase, target_wavs in batches:
             if emb is None or len(emb) == 0:
                 continue
@@ -498,6 +556,13 @@ class Trainer:
             confused = ok & (perm != ident).any(dim=1)
             n_ok = ok.sum().to(torch.float64)
             acc += torch.cat([diag.sum(dim=(0, 2)), torch.stack([n_ok * K, n_ok, confused.sum().to(torch.float64)])])
+            if stoi:
+                d, e, st = metrics.stoi_pair(ref, est.view(B, K, -1), int(acfg["sample_rate"]))
+                zero = torch.zeros_like(d)
+                acc_i += torch.stack([torch.where(st == 0, d, zero).sum(), torch.where(st == 0, e, zero).sum(),
+                                      (st == 0).sum().to(torch.float64)])
+        if stoi:
+            acc = torch.cat([acc, acc_i])
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(acc, group=self.group)
@@ -506,6 +571,9 @@ class Trainer:
         nan = float("nan")
         out = {name: (a[i] / a[3] if a[3] > 0 else nan) for i, name in enumerate(("sdr", "sir", "sar"))}
         out["confusion"] = a[5] / a[4] if a[4] > 0 else nan
+        if stoi:
+            out["stoi"] = a[6] / a[8] if a[8] > 0 else nan
+            out["estoi"] = a[7] / a[8] if a[8] > 0 else nan
         return out
 
     def _with_decisions(self, batches: Iterable):
