@@ -754,6 +754,62 @@ int vs_griffin_lim(const vs_loss_dims* dims, const float* spec, const float* mas
  * sums in the same order: bit-identical results.  Process-wide, like vs_set_option.  Returns 0, or -1 for any other value. */
 int vs_set_griffin_lim_reframe(int mode);
 
+/* ---- ABI 11 (additive entries).  The wavernn and waveglow audio back ends (utils/audio_processor.py:61-438, utils/audio.py:49-135, utils/stft.py:36-99) ----
+ * Both run the transform above (periodic Hann of `win` samples centred in the frame, reflect padding by n_fft/2, 1 + n/hop frames,
+ * |D| = sqrt(re^2 + im^2); the Tacotron conv1d-basis transform is the same sum).  What differs is the codec: how a linear magnitude m
+ * is stored and read back, a pre-emphasis in front of the transform and the padding of Griffin-Lim's inner transform.
+ *   VS_CODEC_DB01    clip((20 log10(max(floor, m)) - ref) / -min_db, -1, 0) + 1                  (voicefilter: vs_wav_to_spec's own)
+ *   VS_CODEC_DBNORM  S = 20 log10(max(floor, m)) - ref  (_amp_to_db :184-186), then _normalize :140-155 under the three flags;
+ *                    decode = _denormalize :157-173 (clip first), 10^((S + ref) / 20)
+ *   VS_CODEC_LOG     ln(max(floor, m)), decode exp(v)                                            (dynamic_range_compression, floor 1e-5)
+ * floor is the caller's: exp(min_level_db / 20 * ln 10) evaluated in fp64 on the host for DBNORM (9.99999999999998e-06 for -100). */
+#define VS_CODEC_DB01 0
+#define VS_CODEC_DBNORM 1
+#define VS_CODEC_LOG 2
+#define VS_PAD_REFLECT 0
+#define VS_PAD_ZERO 1
+typedef struct vs_audio_codec {
+  int kind;                                       /* VS_CODEC_*                                                               */
+  int signal_norm, symmetric_norm, clip_norm;     /* DBNORM only                                                              */
+  int gl_pad;                                     /* padding of Griffin-Lim's inner transform: VS_PAD_REFLECT (wavernn), _ZERO  */
+  int reserved;
+  double floor;                                   /* smallest magnitude the encoder sees                                      */
+  double min_level_db, ref_level_db, max_norm;    /* DB01, DBNORM                                                             */
+  double preemphasis;                             /* 0: none; else p[n] = x[n] - a x[n-1] in front of the transform (x[-1] = 0) */
+} vs_audio_codec;
+
+/* Front end with a codec: wav [B][hop*(T-1)] -> out, phase [B][T][F] (may be NULL).  The pre-emphasis is folded into the framing
+ * gather (the difference formed in fp64 and rounded once; the reflect padding acts on p), the contraction is vs_wav_to_spec's.
+ * mel_basis == NULL: out [B][T][F] = encode(|D|).  Otherwise mel_basis [n_mels][F] fp32 and out [B][T][n_mels] =
+ * encode(mel_basis @ |D|) (melspectrogram / mel_spectrogram), the product as vs_project_floor forms it.  Workspace:
+ * vs_audio_workspace_bytes. */
+int vs_codec_wav_to_spec(const vs_loss_dims* dims, const vs_audio_codec* codec, const float* wav, const float* mel_basis, int n_mels,
+                         float* out, float* phase, void* workspace, size_t workspace_bytes, void* stream);
+/* n stored values (times mask, may be NULL) -> linear fp32 magnitudes, evaluated in fp64 and rounded once; and back. */
+int vs_codec_decode(const vs_audio_codec* codec, const float* spec, const float* mask, long long n, float* mag, void* stream);
+int vs_codec_encode(const vs_audio_codec* codec, const float* mag, long long n, float* spec, void* stream);
+/* out [M][N] = max(floor, in [M][K] @ w [N][K]^T): the mel basis, its pseudo-inverse (floor 1e-10) and mag_to_mel.  fp32 FMAs in
+ * the order k = 0 .. K-1 for every output: within (K + 2) 2^-24 (|w| @ |in|) of the exact product, the same bits for a row
+ * wherever it stands.  in and out must not overlap. */
+int vs_project_floor(const float* in, const float* w, float* out, long long M, int N, int K, float floor, void* stream);
+/* Inverse legs on a LINEAR magnitude [B][T][F]: the iSTFT with a given phase (vs_spec_to_wav behind its decoder), and Griffin-Lim
+ * with the target mag ** power (vs_griffin_lim behind its decoder; pad: the padding of the inner transform, VS_PAD_*; both
+ * re-framing forms of vs_set_griffin_lim_reframe serve both).  Workspaces: vs_audio_workspace_bytes / vs_griffin_lim_workspace_bytes. */
+int vs_mag_to_wav(const vs_loss_dims* dims, const float* mag, const float* phase, float* wav,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int vs_griffin_lim_mag(const vs_loss_dims* dims, const float* mag, const float* init_phase, float power, int n_iter, int pad,
+                       float* wav, double* residual, void* workspace, size_t workspace_bytes, void* stream);
+/* Pre-emphasis y[n] = x[n] - a x[n-1] and its inverse y[n] = x[n] + a y[n-1] (scipy.signal.lfilter([1], [1, -a], x)), rows [B][N]
+ * fp32 in and out, y[-1] = x[-1] = 0, the arithmetic in fp64 and rounded once.  The inverse is a parallel scan: the row is cut into
+ * blocks of vs_deemphasis_block() samples, every block is swept from a zero state, the carries scan per row
+ * (carry(k+1) = a^L carry(k) + last(k)) and a second sweep adds a^(j+1) carry.  The partition and every power of a depend on N and
+ * the sample index alone: a row's bits do not depend on B, on its place in the batch or on where the buffers start.  x and y
+ * must not overlap.  workspace: vs_deemphasis_workspace_bytes(B, N) bytes, 256-byte aligned. */
+int vs_deemphasis_block(void);
+size_t vs_deemphasis_workspace_bytes(int B, long long N);
+int vs_deemphasis(const float* x, float* y, int B, long long N, double coef, void* workspace, size_t workspace_bytes, void* stream);
+int vs_preemphasis(const float* x, float* y, int B, long long N, double coef, void* stream);
+
 /* =============================================================================================
  * Evaluation metric: single-source BSS-eval SDR, the number the reference reports for every test item
  * (utils/generic_utils.py:476-530: mir_eval.separation.bss_eval_sources(clean_wav, est_wav, False)[0][0];

@@ -20,6 +20,8 @@ PROF_NAMES = ("cnn1", "cnn2", "cnn3", "cnn4", "cnn5", "cnn6", "cnn7", "cnn8", "l
               "wgrad_cnn2", "wgrad_cnn3", "wgrad_cnn4", "wgrad_cnn5", "wgrad_cnn6", "wgrad_cnn7",
               "dgrad_cnn2", "dgrad_cnn3", "dgrad_cnn4", "dgrad_cnn5", "dgrad_cnn6", "dgrad_cnn7", "bwd_edge")
 ABI_VERSION = 11
+CODEC_DB01, CODEC_DBNORM, CODEC_LOG = 0, 1, 2
+PAD_REFLECT, PAD_ZERO = 0, 1
 
 
 class VsDims(Structure):
@@ -52,6 +54,11 @@ class VsWsLayout(Structure):
 class VsLossDims(Structure):
     _fields_ = [("B", c_int), ("T", c_int), ("F", c_int), ("n_fft", c_int), ("hop", c_int), ("win", c_int),
                 ("min_level_db", c_float), ("ref_level_db", c_float)]
+
+
+class VsAudioCodec(Structure):
+    _fields_ = [(n, c_int) for n in ("kind", "signal_norm", "symmetric_norm", "clip_norm", "gl_pad", "reserved")] + \
+               [(n, c_double) for n in ("floor", "min_level_db", "ref_level_db", "max_norm", "preemphasis")]
 
 
 class VsSpeakerDims(Structure):
@@ -226,6 +233,17 @@ SIGNATURES = {
     "vs_griffin_lim_workspace_bytes": (c_size_t, [POINTER(VsLossDims)]),
     "vs_griffin_lim": (c_int, [POINTER(VsLossDims), _P, _P, _P, c_float, c_int, _P, _P, _P, c_size_t, _P]),
     "vs_set_griffin_lim_reframe": (c_int, [c_int]),
+    # the wavernn / waveglow audio back ends
+    "vs_codec_wav_to_spec": (c_int, [POINTER(VsLossDims), POINTER(VsAudioCodec), _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "vs_codec_decode": (c_int, [POINTER(VsAudioCodec), _P, _P, c_longlong, _P, _P]),
+    "vs_codec_encode": (c_int, [POINTER(VsAudioCodec), _P, c_longlong, _P, _P]),
+    "vs_project_floor": (c_int, [_P, _P, _P, c_longlong, c_int, c_int, c_float, _P]),
+    "vs_mag_to_wav": (c_int, [POINTER(VsLossDims), _P, _P, _P, _P, c_size_t, _P]),
+    "vs_griffin_lim_mag": (c_int, [POINTER(VsLossDims), _P, _P, c_float, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "vs_deemphasis_block": (c_int, []),
+    "vs_deemphasis_workspace_bytes": (c_size_t, [c_int, c_longlong]),
+    "vs_deemphasis": (c_int, [_P, _P, c_int, c_longlong, c_double, _P, c_size_t, _P]),
+    "vs_preemphasis": (c_int, [_P, _P, c_int, c_longlong, c_double, _P]),
     "vs_sigmoid_bwd": (c_int, [_P, _P, _P, c_longlong, _P]),
     "vs_colsum": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     # evaluation metric

@@ -7,13 +7,20 @@ model for the "voicefilter" audio backend,
 
 as calls into libvoicesplit_hip.so: the STFT / iSTFT run as one GEMM against a windowed DFT basis
 plus a gather (the analysis window is 400 of the 1200 frame samples, so the dense basis is small).
+
+The other two back ends of ``WrapperAudioProcessor`` (``wavernn``, ``waveglow``: utils/audio_processor.py:61-438) run the same
+transform with another codec around it (csrc/audio_codec.hip): every entry point below passes its ``audio_cfg`` through ``resolve``,
+and ``AudioProcessor`` mirrors the wrapper class on device tensors.
 """
 import ctypes
 import math
 
 import torch
 
+import numpy as np
+
 from . import _lib
+from .config import resolve_audio as resolve
 from .losses import loss_dims
 from .ops import _dev_check, _p, _stream
 
@@ -41,6 +48,9 @@ def frames_for(n_samples: int, hop: int) -> int:
 
 def wav_to_spec(wav: torch.Tensor, audio_cfg, want_phase: bool = True):
     """wav [B, hop*(T-1)] -> (spec [B,T,F] normalised dB magnitude in [0,1], phase [B,T,F] or None)."""
+    audio_cfg = resolve(audio_cfg)
+    if _foreign(audio_cfg):
+        return _codec_wav_to_spec(wav, audio_cfg, want_phase, bool(audio_cfg["mel_spec"]))
     lib = _lib.load()
     _dev_check(wav, "wav")
     B, S = wav.shape
@@ -58,13 +68,22 @@ def wav_to_spec(wav: torch.Tensor, audio_cfg, want_phase: bool = True):
     return spec, phase
 
 
-def spec_to_wav(spec: torch.Tensor, phase: torch.Tensor = None, audio_cfg=None, mask: torch.Tensor = None) -> torch.Tensor:
+def spec_to_wav(spec: torch.Tensor, phase: torch.Tensor = None, audio_cfg=None, mask: torch.Tensor = None,
+                generator: torch.Generator = None) -> torch.Tensor:
     """(spec * mask), phase [B,T,F] -> wav [B, hop*(T-1)] (ap.inv_spectrogram with the given phase).  phase=None is the
-    reference's ``ap.inv_spectrogram(spec)``: ``griffin_lim`` with the config's ``power`` and ``griffin_lim_iters``."""
+    reference's ``ap.inv_spectrogram(spec)``: ``griffin_lim`` with the config's ``power`` and ``griffin_lim_iters`` (its random
+    starting angles drawn from ``generator``).
+
+    Under a wavernn or waveglow block the reference's ``inv_spectrogram`` DROPS the phase argument and always runs Griffin-Lim
+    (utils/audio_processor.py:217-222, 394-402); here a given phase inverts with it (decode -> [mel -> linear] -> iSTFT ->
+    de-emphasis where the block has a pre-emphasis).  That is this package's extension: pass phase=None for the reference's result."""
     if audio_cfg is None:
         raise TypeError("spec_to_wav: audio_cfg is required")
+    audio_cfg = resolve(audio_cfg)
     if phase is None:
-        return griffin_lim(spec, audio_cfg, mask=mask)
+        return griffin_lim(spec, audio_cfg, mask=mask, generator=generator)
+    if _foreign(audio_cfg):
+        return _deemphasised(mag_to_wav(_linear_target(spec, audio_cfg, mask), phase, audio_cfg), audio_cfg)
     lib = _lib.load()
     for n, t in (("spec", spec), ("phase", phase)):
         _dev_check(t, n)
@@ -86,7 +105,14 @@ def griffin_lim(spec: torch.Tensor, audio_cfg, n_iter: int = None, power: float 
     516-523 in one resident loop on the device (vs_griffin_lim).  n_iter / power default to ``audio_cfg["griffin_lim_iters"]`` /
     ``audio_cfg["power"]``; init_phase=None draws ``2*pi*torch.rand`` on the device from ``generator`` (the reference's
     ``np.random.rand`` angles).  Started from a mixture's phase with power=1 it is the consistency refinement of a masked
-    spectrogram.  return_residual: also ``|| |stft(y_i)| - S || / || S ||`` per iteration and item, fp64 [n_iter, B]."""
+    spectrogram.  return_residual: also ``|| |stft(y_i)| - S || / || S ||`` per iteration and item, fp64 [n_iter, B].
+    Under a wavernn or waveglow block: decode -> [mel -> linear] -> ``griffin_lim_mag`` (the inner transform pads as the block's
+    processor does) -> de-emphasis where the block has a pre-emphasis (inv_linear_spectrogram / inv_mel_spectrogram)."""
+    audio_cfg = resolve(audio_cfg)
+    if _foreign(audio_cfg):
+        out = griffin_lim_mag(_linear_target(spec, audio_cfg, mask), audio_cfg, n_iter=n_iter, power=power, init_phase=init_phase,
+                              generator=generator, return_residual=return_residual)
+        return (_deemphasised(out[0], audio_cfg), out[1]) if return_residual else _deemphasised(out, audio_cfg)
     lib = _lib.load()
     _dev_check(spec, "spec")
     if mask is not None:
@@ -108,6 +134,303 @@ def griffin_lim(spec: torch.Tensor, audio_cfg, n_iter: int = None, power: float 
                                 _p(ws), ws.numel(), _stream())
     _lib.check(rc, "vs_griffin_lim")
     return (wav, res) if return_residual else wav
+
+
+# ---- the wavernn and waveglow back ends: codec, mel projection, inverse legs on a linear magnitude (csrc/audio_codec.hip) -----------
+_CODEC_KINDS = {"DB01": _lib.CODEC_DB01, "DBNORM": _lib.CODEC_DBNORM, "LOG": _lib.CODEC_LOG}
+_PADS = {"reflect": _lib.PAD_REFLECT, "zero": _lib.PAD_ZERO}
+_MEL = {}
+
+
+def _foreign(cfg) -> bool:
+    return cfg.get("backend", "voicefilter") != "voicefilter"
+
+
+def _refuse_foreign(audio_cfg, who: str):
+    cfg = resolve(audio_cfg)
+    if _foreign(cfg):
+        raise ValueError(f"{who}: the {cfg['backend']} audio back end is not streamed (its inverse is Griffin-Lim over the whole clip); "
+                         "use the voicefilter block")
+
+
+def codec_of(audio_cfg) -> dict:
+    """The codec of a block: ``resolve(block)['codec']``, or the voicefilter processor's DB01 (amp_to_db, normalize :537-547)."""
+    cfg = resolve(audio_cfg)
+    if "codec" in cfg:
+        return cfg["codec"]
+    return {"kind": "DB01", "floor": 1e-5, "min_level_db": float(cfg.get("min_level_db", -100.0)),
+            "ref_level_db": float(cfg.get("ref_level_db", 20.0)), "signal_norm": False, "symmetric_norm": False, "clip_norm": False,
+            "max_norm": 1.0, "preemphasis": 0.0, "gl_pad": "reflect"}
+
+
+def _codec_struct(codec) -> "_lib.VsAudioCodec":
+    return _lib.VsAudioCodec(_CODEC_KINDS[codec["kind"]], int(bool(codec["signal_norm"])), int(bool(codec["symmetric_norm"])),
+                             int(bool(codec["clip_norm"])), _PADS[codec["gl_pad"]], 0, float(codec["floor"]),
+                             float(codec["min_level_db"]), float(codec["ref_level_db"]), float(codec["max_norm"]),
+                             float(codec["preemphasis"]))
+
+
+def mel_basis(audio_cfg, device) -> torch.Tensor:
+    """[num_mels, F] fp32 on ``device``: ``librosa.filters.mel(sample_rate, n_fft, num_mels, mel_fmin, mel_fmax)`` as
+    ``speaker.mel_filterbank`` restates it, rounded to fp32 (kept per device and settings)."""
+    return _mel(audio_cfg, device)[0]
+
+
+def mel_pinv(audio_cfg, device) -> torch.Tensor:
+    """[F, num_mels] fp32: ``np.linalg.pinv`` of the fp32 basis, taken in fp64 and rounded (``_mel_to_linear``)."""
+    return _mel(audio_cfg, device)[1]
+
+
+def _mel(audio_cfg, device):
+    from .speaker import mel_filterbank
+    cfg = resolve(audio_cfg)
+    key = (torch.device(device).index, int(cfg.get("sample_rate", 16000)), int(cfg["n_fft"]), int(cfg.get("num_mels", 80)),
+           float(cfg.get("mel_fmin") or 0.0), cfg.get("mel_fmax"))
+    if key not in _MEL:
+        w = mel_filterbank(key[1], key[2], key[3], key[4], key[5]).to(torch.float32)
+        inv = torch.from_numpy(np.linalg.pinv(w.double().numpy())).to(torch.float32)
+        _MEL[key] = (w.to(device).contiguous(), inv.to(device).contiguous())
+    return _MEL[key]
+
+
+def decode(spec: torch.Tensor, audio_cfg, mask: torch.Tensor = None) -> torch.Tensor:
+    """Stored values (times mask) -> linear fp32 magnitudes of the same shape, under the block's codec; evaluated in fp64 on the
+    device and rounded once."""
+    lib = _lib.load()
+    _dev_check(spec, "spec")
+    if mask is not None:
+        _dev_check(mask, "mask")
+        if mask.shape != spec.shape:
+            raise ValueError(f"mask must have the shape of spec {tuple(spec.shape)}")
+    c = _codec_struct(codec_of(audio_cfg))
+    out = torch.empty_like(spec)
+    with torch.cuda.device(spec.device):
+        rc = lib.vs_codec_decode(ctypes.byref(c), _p(spec), _p(mask), spec.numel(), _p(out), _stream())
+    _lib.check(rc, "vs_codec_decode")
+    return out
+
+
+def encode(mag: torch.Tensor, audio_cfg) -> torch.Tensor:
+    """Linear magnitudes -> stored values of the block's codec (``max(floor, .)`` first)."""
+    lib = _lib.load()
+    _dev_check(mag, "mag")
+    c = _codec_struct(codec_of(audio_cfg))
+    out = torch.empty_like(mag)
+    with torch.cuda.device(mag.device):
+        rc = lib.vs_codec_encode(ctypes.byref(c), _p(mag), mag.numel(), _p(out), _stream())
+    _lib.check(rc, "vs_codec_encode")
+    return out
+
+
+def project(x: torch.Tensor, w: torch.Tensor, floor: float = 0.0) -> torch.Tensor:
+    """``max(floor, x @ w.T)``: x [..., K], w [N, K] -> [..., N], one fp32 FMA chain per output in the order of K."""
+    lib = _lib.load()
+    _dev_check(x, "x")
+    _dev_check(w, "w")
+    if w.dim() != 2 or x.shape[-1] != w.shape[1]:
+        raise ValueError(f"project: x {tuple(x.shape)} against w {tuple(w.shape)}")
+    out = torch.empty(*x.shape[:-1], w.shape[0], device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.vs_project_floor(_p(x), _p(w), _p(out), x.numel() // x.shape[-1], w.shape[0], w.shape[1], float(floor), _stream())
+    _lib.check(rc, "vs_project_floor")
+    return out
+
+
+def mel_to_linear(mel_mag: torch.Tensor, audio_cfg) -> torch.Tensor:
+    """``np.maximum(1e-10, pinv(mel_basis) @ S)`` on linear mel magnitudes [..., num_mels] -> [..., F]."""
+    return project(mel_mag, mel_pinv(audio_cfg, mel_mag.device), 1e-10)
+
+
+def _linear_target(spec, cfg, mask=None):
+    """The linear magnitude [B,T,F] the inverse legs start from: decode, then mel -> linear under ``mel_spec``."""
+    mag = decode(spec, cfg, mask)
+    return mel_to_linear(mag, cfg) if cfg.get("mel_spec") else mag
+
+
+def _deemphasised(wav, cfg):
+    a = float(codec_of(cfg)["preemphasis"])
+    return deemphasis(wav, a) if a != 0.0 else wav
+
+
+def _codec_wav_to_spec(wav, cfg, want_phase, mel):
+    lib = _lib.load()
+    _dev_check(wav, "wav")
+    B, S = wav.shape
+    hop = int(cfg["hop_length"])
+    if S % hop:
+        raise ValueError(f"wav length {S} must be a multiple of hop_length {hop} (crop or pad the clip)")
+    T, F = S // hop + 1, int(cfg["n_fft"]) // 2 + 1
+    d = loss_dims(B, T, F, cfg)
+    c = _codec_struct(codec_of(cfg))
+    ws = _workspace(d, wav.device)
+    basis = mel_basis(cfg, wav.device) if mel else None
+    n_mels = int(basis.shape[0]) if mel else 0
+    spec = torch.empty(B, T, n_mels if mel else F, device=wav.device)
+    phase = torch.empty(B, T, F, device=wav.device) if want_phase else None
+    with torch.cuda.device(wav.device):
+        rc = lib.vs_codec_wav_to_spec(ctypes.byref(d), ctypes.byref(c), _p(wav), _p(basis), n_mels, _p(spec), _p(phase), _p(ws),
+                                      ws.numel(), _stream())
+    _lib.check(rc, "vs_codec_wav_to_spec")
+    return spec, phase
+
+
+def wav_to_mel(wav: torch.Tensor, audio_cfg):
+    """wav [B, hop*(T-1)] -> [B, T, num_mels] = encode(mel_basis @ |D|) (melspectrogram / mel_spectrogram), whatever ``mel_spec``."""
+    cfg = resolve(audio_cfg)
+    if not _foreign(cfg):
+        raise ValueError("wav_to_mel: the voicefilter block has no mel spectrogram of this form; speaker.logmel is its get_mel")
+    return _codec_wav_to_spec(wav, cfg, False, True)[0]
+
+
+def mag_to_wav(mag: torch.Tensor, phase: torch.Tensor, audio_cfg) -> torch.Tensor:
+    """A LINEAR magnitude and a phase [B,T,F] -> wav [B, hop*(T-1)]: ``spec_to_wav`` behind its decoder (no de-emphasis)."""
+    lib = _lib.load()
+    for n, t in (("mag", mag), ("phase", phase)):
+        _dev_check(t, n)
+    if phase.shape != mag.shape:
+        raise ValueError(f"phase must have the shape of mag {tuple(mag.shape)}")
+    B, T, F = mag.shape
+    d = loss_dims(B, T, F, audio_cfg)
+    ws = _workspace(d, mag.device)
+    wav = torch.empty(B, d.hop * (T - 1), device=mag.device)
+    with torch.cuda.device(mag.device):
+        rc = lib.vs_mag_to_wav(ctypes.byref(d), _p(mag), _p(phase), _p(wav), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "vs_mag_to_wav")
+    return wav
+
+
+def griffin_lim_mag(mag: torch.Tensor, audio_cfg, n_iter: int = None, power: float = None, init_phase: torch.Tensor = None,
+                    pad: str = None, generator: torch.Generator = None, return_residual: bool = False):
+    """``_griffin_lim(mag ** power)`` on a LINEAR magnitude [B,T,F] -> wav [B, hop*(T-1)] (no de-emphasis).  pad: "reflect" or "zero",
+    the padding of the inner transform (None: the block's own: zeros for waveglow, utils/audio_processor.py:411-418).  The other
+    arguments as in ``griffin_lim``."""
+    lib = _lib.load()
+    cfg = resolve(audio_cfg)
+    _dev_check(mag, "mag")
+    n_iter = int(cfg["griffin_lim_iters"] if n_iter is None else n_iter)
+    power = float(cfg["power"] if power is None else power)
+    pad = codec_of(cfg)["gl_pad"] if pad is None else pad
+    if pad not in _PADS:
+        raise ValueError(f"griffin_lim_mag: pad {pad!r} is not one of {tuple(_PADS)}")
+    if init_phase is None:
+        init_phase = 2.0 * math.pi * torch.rand(mag.shape, device=mag.device, dtype=torch.float32, generator=generator)
+    _dev_check(init_phase, "init_phase")
+    if init_phase.shape != mag.shape:
+        raise ValueError(f"init_phase must have the shape of mag {tuple(mag.shape)}")
+    B, T, F = mag.shape
+    d = loss_dims(B, T, F, cfg)
+    ws = _workspace(d, mag.device, "vs_griffin_lim_workspace_bytes")
+    wav = torch.empty(B, d.hop * (T - 1), device=mag.device)
+    res = torch.empty(max(n_iter, 0), B, dtype=torch.float64, device=mag.device) if return_residual else None
+    with torch.cuda.device(mag.device):
+        rc = lib.vs_griffin_lim_mag(ctypes.byref(d), _p(mag), _p(init_phase), power, n_iter, _PADS[pad], _p(wav), _p(res),
+                                    _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "vs_griffin_lim_mag")
+    return (wav, res) if return_residual else wav
+
+
+_DE_WS = {}
+
+
+def deemphasis_block() -> int:
+    """Samples per block of the de-emphasis scan (``vs_deemphasis_block``)."""
+    return int(_lib.load().vs_deemphasis_block())
+
+
+def _rows(wav):
+    if wav.dim() not in (1, 2) or wav.numel() == 0:
+        raise ValueError(f"wav must be [n] or [B, n] and not empty, got {tuple(wav.shape)}")
+    return wav.reshape(-1, wav.shape[-1])
+
+
+def deemphasis(wav: torch.Tensor, coef: float) -> torch.Tensor:
+    """y[n] = wav[n] + coef * y[n-1], y[-1] = 0 (``scipy.signal.lfilter([1], [1, -coef], wav)``, apply_inv_preemphasis) on wav [n] or
+    [B, n]: a two-sweep scan in fp64 (vs_deemphasis); a row's bits do not depend on the batch around it."""
+    lib = _lib.load()
+    _dev_check(wav, "wav")
+    x = _rows(wav)
+    B, N = x.shape
+    n = lib.vs_deemphasis_workspace_bytes(B, N)
+    if n == 0:
+        _lib.check(-1, "vs_deemphasis_workspace_bytes")
+    key = torch.device(wav.device).index
+    ws = _DE_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _DE_WS[key] = torch.empty(n, dtype=torch.uint8, device=wav.device)
+    y = torch.empty_like(wav)
+    with torch.cuda.device(wav.device):
+        rc = lib.vs_deemphasis(_p(x), _p(y), B, N, float(coef), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "vs_deemphasis")
+    return y
+
+
+def preemphasis(wav: torch.Tensor, coef: float) -> torch.Tensor:
+    """y[n] = wav[n] - coef * wav[n-1], wav[-1] = 0 (``lfilter([1, -coef], [1], wav)``, apply_preemphasis) on wav [n] or [B, n]; the
+    difference in fp64, rounded once.  (The front end forms it inside its framing gather; this is the stand-alone filter.)"""
+    lib = _lib.load()
+    _dev_check(wav, "wav")
+    x = _rows(wav)
+    y = torch.empty_like(wav)
+    with torch.cuda.device(wav.device):
+        rc = lib.vs_preemphasis(_p(x), _p(y), x.shape[0], x.shape[1], float(coef), _stream())
+    _lib.check(rc, "vs_preemphasis")
+    return y
+
+
+class AudioProcessor:
+    """``WrapperAudioProcessor(config.audio)`` (utils/audio_processor.py:19-59) on device tensors, for the three back ends.
+    Spectrograms are [time, freq] as the reference returns them; a waveform is [n] (one clip, as the reference takes it) or [B, n]
+    with n a multiple of hop_length, and a batch dimension is carried through.  ``mel_spec`` (``config.audio['mel_spec']``) is
+    honoured: ``get_spec_from_audio`` then returns mel features and ``inv_spectrogram`` takes them.
+
+    Departures: ``get_spec_from_audio(wav, return_phase=True)`` returns the transform's phase for every back end (the reference
+    returns None for wavernn / waveglow), and ``inv_spectrogram`` inverts with a phase when one is given (the reference drops it
+    for those two); ``init_phase`` / ``generator`` choose Griffin-Lim's starting angles (``np.random.rand`` in the reference).
+    Not here: load_wav, save_wav, do_trim_silence, the mu-law / quantisation helpers and the [-1, 1] input asserts."""
+
+    def __init__(self, config_audio):
+        self.cfg = resolve(config_audio)
+        self.backend = self.cfg.get("backend", "voicefilter")
+        self.mel_spec = bool(self.cfg.get("mel_spec", False)) and self.backend != "voicefilter"
+        self.sample_rate = int(self.cfg.get("sample_rate", 16000))
+        self.n_fft, self.hop_length, self.win_length = (int(self.cfg[k]) for k in ("n_fft", "hop_length", "win_length"))
+
+    @staticmethod
+    def _batched(t, dims):
+        return (t, False) if t.dim() == dims else (t[None], True)
+
+    def get_spec_from_audio(self, wav: torch.Tensor, return_phase: bool = False):
+        x, one = self._batched(wav, 2)
+        spec, phase = wav_to_spec(x.contiguous(), self.cfg, want_phase=return_phase)
+        if one:
+            spec, phase = spec[0], (phase[0] if phase is not None else None)
+        return (spec, phase) if return_phase else spec
+
+    def inv_spectrogram(self, spec: torch.Tensor, phase: torch.Tensor = None, init_phase: torch.Tensor = None,
+                        generator: torch.Generator = None) -> torch.Tensor:
+        s, one = self._batched(spec, 3)
+        if phase is not None:
+            wav = spec_to_wav(s.contiguous(), self._batched(phase, 3)[0].contiguous(), self.cfg)
+        else:
+            ip = None if init_phase is None else self._batched(init_phase, 3)[0].contiguous()
+            wav = griffin_lim(s.contiguous(), self.cfg, init_phase=ip, generator=generator)
+        return wav[0] if one else wav
+
+    def get_mel(self, wav: torch.Tensor) -> torch.Tensor:
+        """waveglow ``get_mel`` / wavernn ``melspectrogram``: [T, num_mels]; voicefilter: the log-mel of ``speaker.logmel``."""
+        if self.backend == "voicefilter":
+            from .speaker import logmel
+            return logmel(wav, self.cfg, int(self.cfg.get("num_mels", 40)))
+        x, one = self._batched(wav, 2)
+        mel = wav_to_mel(x.contiguous(), self.cfg)
+        return mel[0] if one else mel
+
+    def mag_to_mel(self, y: torch.Tensor) -> torch.Tensor:
+        """Stored linear-frequency values [T, F] -> stored mel values [T, num_mels]: encode(mel_basis @ decode(y))
+        (mag_to_mel_spectrogram, utils/audio.py:119-135)."""
+        if self.backend == "voicefilter":
+            raise ValueError("mag_to_mel: the voicefilter audio back end has no mel form of its spectrogram")
+        return encode(project(decode(y.contiguous(), self.cfg), mel_basis(self.cfg, y.device)), self.cfg)
 
 
 _RESAMPLERS = {}
@@ -142,6 +465,7 @@ def separate(model, wav: torch.Tensor, dvec: torch.Tensor, audio_cfg, refine_ite
     loudness: None, or the level in LUFS of the corpus the network was trained on: every row is first brought there
     (``loudness.normalize_clips_`` at the rate of ``wav``: BS.1770 integrated loudness, one linear gain g under a -2 dB peak cap) and
     the estimate is returned at the input's own level, multiplied by fp32(1 / g).  Rows without a loudness keep g = 1."""
+    audio_cfg = resolve(audio_cfg)
     own = int(audio_cfg.get("sample_rate", 16000))
     if loudness is not None:
         from .loudness import _rows_table, normalize_clips_
@@ -235,6 +559,7 @@ class StreamingSeparator:
 
     def __init__(self, model, dvec: torch.Tensor, audio_cfg, C: int, R: int, trace: bool = False):
         from .streaming import StreamingMasker
+        _refuse_foreign(audio_cfg, "StreamingSeparator")
         self.K = int(dvec.shape[1]) if dvec.dim() == 3 else None      # None: one speaker per stream, [B, n] out
         self.mask_trace = [] if trace else None  # trace: every block of mask rows, in order
         self.cfg = audio_cfg
@@ -346,6 +671,7 @@ class StreamingSeparatorAtRate:
 
     def __init__(self, model, dvec: torch.Tensor, audio_cfg, C: int, R: int, sample_rate: int):
         from .resample import StreamingResampler
+        _refuse_foreign(audio_cfg, "StreamingSeparatorAtRate")
         own = int(audio_cfg.get("sample_rate", 16000))
         self.sample_rate, self.own_rate = int(sample_rate), own
         self.hop = int(audio_cfg["hop_length"])
@@ -439,6 +765,9 @@ def separate_many(model, wavs, dvecs: torch.Tensor, audio_cfg, max_items: int = 
     (clips, and clips x longest clip in frames): the workspace grows with the latter, about 0.36 MB per frame at full width."""
     if len(wavs) != dvecs.shape[0]:
         raise ValueError(f"{len(wavs)} waveforms for {dvecs.shape[0]} d-vectors")
+    audio_cfg = resolve(audio_cfg)
+    if audio_cfg.get("mel_spec"):
+        raise ValueError("separate_many: forward_ragged takes linear spectrograms; the audio block has mel_spec set")
     groups = {}
     for i, w in enumerate(wavs):
         if w.dim() != 1:

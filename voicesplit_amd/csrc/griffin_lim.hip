@@ -26,6 +26,8 @@ __device__ __forceinline__ double gl_block_sum(double v) {
 }
 
 // vmax[item] = bits of max clip(a*b, 0, 1) over the item (S is monotone in it): one integer atomicMax per wave
+// LINEAR (vs_griffin_lim_mag): a is a linear magnitude, the maximum is that of |a|
+template <bool LINEAR>
 __global__ __launch_bounds__(256)
 void gl_item_max_kernel(const float* __restrict__ a, const float* __restrict__ b, unsigned* __restrict__ vmax, VsStftShape s) {
   const int item = blockIdx.y;
@@ -34,8 +36,12 @@ void gl_item_max_kernel(const float* __restrict__ a, const float* __restrict__ b
   float m = 0.f;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     float v = a[base + i];
-    if (b) v *= b[base + i];
-    m = fmaxf(m, fminf(fmaxf(v, 0.f), 1.f));
+    if constexpr (LINEAR) {
+      m = fmaxf(m, fabsf(v));
+    } else {
+      if (b) v *= b[base + i];
+      m = fmaxf(m, fminf(fmaxf(v, 0.f), 1.f));
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
@@ -51,6 +57,8 @@ void gl_item_max_kernel(const float* __restrict__ a, const float* __restrict__ b
 // S * (re * rsqrt) -- covered by the scale rule of scale_from_absmax_kernel, which puts the bound in [2^9, 2^10), a factor 64 below
 // f16's largest value) and den[b] += sum S^2.
 // grid (gx, B): a workgroup stays inside one item.
+// LINEAR (vs_griffin_lim_mag): S = |a|^power, a a linear magnitude (np.abs(S ** power) of _griffin_lim's callers)
+template <bool LINEAR>
 __global__ __launch_bounds__(256)
 void gl_target_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ phase, float power,
                       float* __restrict__ S, float* __restrict__ reim, double* __restrict__ den, VsStftShape s,
@@ -60,7 +68,8 @@ void gl_target_kernel(const float* __restrict__ a, const float* __restrict__ b, 
   const size_t base = (size_t)item * n;
   const double kpow = 0.11512925464970228 * (double)power;      // ln(10) / 20 * power
   int e = 0;
-  (void)frexp(exp((((double)__uint_as_float(vmax[item]) - 1.0) * (-(double)s.min_level_db) + (double)s.ref_level_db) * kpow), &e);
+  if constexpr (LINEAR) (void)frexp(pow((double)__uint_as_float(vmax[item]), (double)power), &e);
+  else (void)frexp(exp((((double)__uint_as_float(vmax[item]) - 1.0) * (-(double)s.min_level_db) + (double)s.ref_level_db) * kpow), &e);
   e = e > 120 ? 120 : (e < -120 ? -120 : e);
   const double level = ldexp(1.0, -e);
   if (blockIdx.x == 0 && threadIdx.x == 0) gain[item] = ldexpf(1.f, e);
@@ -71,9 +80,14 @@ void gl_target_kernel(const float* __restrict__ a, const float* __restrict__ b, 
     const size_t row = ((size_t)item * s.T + t) * s.ldk;
     // in fp64, once per call: S is what every round is measured against (an fp32 dB value alone is only good to ~7e-7 of S)
     double v = a[base + i];
-    if (b) v *= (double)b[base + i];
-    const double db = (fmin(fmax(v, 0.0), 1.0) - 1.0) * (-(double)s.min_level_db) + (double)s.ref_level_db;
-    const float mag = (float)(exp(db * kpow) * level);
+    float mag;
+    if constexpr (LINEAR) {
+      mag = (float)(pow(fabs(v), (double)power) * level);
+    } else {
+      if (b) v *= (double)b[base + i];
+      const double db = (fmin(fmax(v, 0.0), 1.0) - 1.0) * (-(double)s.min_level_db) + (double)s.ref_level_db;
+      mag = (float)(exp(db * kpow) * level);
+    }
     float sn, cs;
     sincosf(phase[base + i], &sn, &cs);
     S[base + i] = mag;
@@ -128,6 +142,8 @@ void gl_project_kernel(float* __restrict__ reim, const float* __restrict__ S, do
 
 // overlap_add_kernel and stft_frames_kernel in one launch: out[m][j] = w[j] * y[b][reflect(hop*t - lead + j)] with
 // y[b][sp] = (sum_t' in[b*T+t'][sp - hop*t' + lead]) / env[sp] formed on the fly (the same sums in the same order: the same bits).
+// ZERO: the clip is padded with zeros instead of its reflection (stft_frames_kernel<true>).
+template <bool ZERO>
 __global__ __launch_bounds__(256)
 void gl_reframe_kernel(const float* __restrict__ in, const float* __restrict__ env, float* __restrict__ out, VsStftShape s,
                        unsigned* __restrict__ amax) {
@@ -138,9 +154,14 @@ void gl_reframe_kernel(const float* __restrict__ in, const float* __restrict__ e
     const int j = (int)(i - m * s.win);
     const int b = (int)(m / s.T), t = (int)(m - (long long)b * s.T);
     int sp = s.hop * t - s.lead + j;
-    if (sp < 0) sp = -sp;
-    if (sp >= s.S) sp = 2 * (s.S - 1) - sp;
-    const float v = hann_w(j, s) * (stft_gather(in, b, sp, s) / env[sp]);
+    float v;
+    if constexpr (ZERO) {
+      v = (sp < 0 || sp >= s.S) ? 0.f : hann_w(j, s) * (stft_gather(in, b, sp, s) / env[sp]);
+    } else {
+      if (sp < 0) sp = -sp;
+      if (sp >= s.S) sp = 2 * (s.S - 1) - sp;
+      v = hann_w(j, s) * (stft_gather(in, b, sp, s) / env[sp]);
+    }
     out[i] = v;
     mx = fmaxf(mx, fabsf(v));
   }
@@ -167,6 +188,11 @@ __global__ void gl_residual_kernel(double* __restrict__ res, const double* __res
 
 int g_gl_reframe = 0;      // vs_set_griffin_lim_reframe
 
+// vs_griffin_lim (linear = false: spec, mask are stored dB01 values) and vs_griffin_lim_mag (linear = true: spec is a linear
+// magnitude, mask NULL; zero_pad: the inner transform pads the clip with zeros)
+int gl_run(const vs_loss_dims* d, const float* spec, const float* mask, bool linear, bool zero_pad, const float* init_phase, float power,
+           int n_iter, float* wav, double* residual, void* ws, size_t ws_bytes, hipStream_t stream);
+
 }  // namespace
 
 extern "C" {
@@ -181,7 +207,21 @@ int vs_set_griffin_lim_reframe(int mode) {
 
 int vs_griffin_lim(const vs_loss_dims* d, const float* spec, const float* mask, const float* init_phase, float power, int n_iter,
                    float* wav, double* residual, void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+  return gl_run(d, spec, mask, false, false, init_phase, power, n_iter, wav, residual, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+int vs_griffin_lim_mag(const vs_loss_dims* d, const float* mag, const float* init_phase, float power, int n_iter, int pad,
+                       float* wav, double* residual, void* ws, size_t ws_bytes, void* stream_) {
+  VS_REQUIRE(pad == VS_PAD_REFLECT || pad == VS_PAD_ZERO, "griffin_lim_mag: pad=%d (0 = reflect, 1 = zeros)", pad);
+  return gl_run(d, mag, nullptr, true, pad == VS_PAD_ZERO, init_phase, power, n_iter, wav, residual, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+}  // extern "C"
+
+namespace {
+
+int gl_run(const vs_loss_dims* d, const float* spec, const float* mask, bool linear, bool zero_pad, const float* init_phase, float power,
+           int n_iter, float* wav, double* residual, void* ws, size_t ws_bytes, hipStream_t stream) {
   VsStftShape s;
   if (int rc = vs_stft_make_shape(d, &s)) return rc;
   s.periodic = 1;
@@ -225,19 +265,26 @@ int vs_griffin_lim(const vs_loss_dims* d, const float* spec, const float* mask, 
   auto istft = [&](float* out) {      // out[M][win] = reim[M][K] @ basis[win][K]^T
     return vs_stft_contract(split, 0, reim, s.ldk, basis, s.ldk, out, s.win, M, s.win, s.K, scales + 2, scales + 4, stream);
   };
-  hipLaunchKernelGGL(gl_item_max_kernel, dim3(gx, s.B), dim3(256), 0, stream, spec, mask, vmax, s);
-  hipLaunchKernelGGL(gl_target_kernel, dim3(gx, s.B), dim3(256), 0, stream, spec, mask, init_phase, power, S, reim, den, s,
-                     split ? amax + VS_AMAX_SLOTS : nullptr, vmax, gain);
+  if (linear) {
+    hipLaunchKernelGGL(gl_item_max_kernel<true>, dim3(gx, s.B), dim3(256), 0, stream, spec, mask, vmax, s);
+    hipLaunchKernelGGL(gl_target_kernel<true>, dim3(gx, s.B), dim3(256), 0, stream, spec, mask, init_phase, power, S, reim, den, s,
+                       split ? amax + VS_AMAX_SLOTS : nullptr, vmax, gain);
+  } else {
+    hipLaunchKernelGGL(gl_item_max_kernel<false>, dim3(gx, s.B), dim3(256), 0, stream, spec, mask, vmax, s);
+    hipLaunchKernelGGL(gl_target_kernel<false>, dim3(gx, s.B), dim3(256), 0, stream, spec, mask, init_phase, power, S, reim, den, s,
+                       split ? amax + VS_AMAX_SLOTS : nullptr, vmax, gain);
+  }
   if (split) if (int rc = vs_scale_from_absmax_impl(amax + VS_AMAX_SLOTS, VS_AMAX_SLOTS, scales + 2, stream)) return rc;
   if (int rc = istft(frames)) return rc;
   for (int it = 0; it < n_iter; ++it) {
     float* cur = frames;
     if (gather) {
-      hipLaunchKernelGGL(gl_reframe_kernel, dim3(gfr), dim3(256), 0, stream, frames, env, frames2, s, split ? amax : nullptr);
+      if (zero_pad) hipLaunchKernelGGL(gl_reframe_kernel<true>, dim3(gfr), dim3(256), 0, stream, frames, env, frames2, s, split ? amax : nullptr);
+      else hipLaunchKernelGGL(gl_reframe_kernel<false>, dim3(gfr), dim3(256), 0, stream, frames, env, frames2, s, split ? amax : nullptr);
       cur = frames2;
     } else {
       vs_overlap_add_launch(frames, env, wav, s, stream);
-      vs_stft_frames_launch(wav, frames, s, split ? amax : nullptr, gfr, stream);
+      vs_stft_frames_launch(wav, frames, s, split ? amax : nullptr, gfr, stream, zero_pad ? 1 : 0);
     }
     if (split) if (int rc = vs_scale_from_absmax_impl(amax, VS_AMAX_SLOTS, scales, stream)) return rc;
     if (int rc = vs_stft_contract(split, 0, cur, s.win, fbasis, s.win, reim, s.ldk, M, s.K, s.win, scales, scales + 6, stream)) return rc;
@@ -251,4 +298,4 @@ int vs_griffin_lim(const vs_loss_dims* d, const float* spec, const float* mask, 
   return 0;
 }
 
-}  // extern "C"
+}  // namespace

@@ -84,6 +84,8 @@ void spec_to_reim_kernel(const float* __restrict__ a, const float* __restrict__ 
 // frames[m][j] = w[j] * wav_reflect[b][hop*t - lead + j]     (librosa.stft: center=True, reflect padding;
 // only the win samples under the centred window matter).  The clip ends where it ends: reflection about sample S - 1, and
 // S > n_fft / 2 (every caller requires it) makes one reflection enough: the index never leaves [0, S).
+// ZERO: librosa's pad_mode='constant' instead (the waveglow Griffin-Lim): a sample outside the clip is 0.
+template <bool ZERO>
 __global__ __launch_bounds__(256)
 void stft_frames_kernel(const float* __restrict__ wav, float* __restrict__ frames, VsStftShape s, unsigned* __restrict__ amax = nullptr) {
   const long long n = (long long)s.B * s.T * s.win;
@@ -93,9 +95,14 @@ void stft_frames_kernel(const float* __restrict__ wav, float* __restrict__ frame
     const int j = (int)(i - m * s.win);
     const int b = (int)(m / s.T), t = (int)(m - (long long)b * s.T);
     int idx = s.hop * t - s.lead + j;
-    if (idx < 0) idx = -idx;
-    if (idx >= s.S) idx = 2 * (s.S - 1) - idx;
-    const float v = hann_w(j, s) * wav[(size_t)b * s.S + idx];
+    float v;
+    if constexpr (ZERO) {
+      v = (idx < 0 || idx >= s.S) ? 0.f : hann_w(j, s) * wav[(size_t)b * s.S + idx];
+    } else {
+      if (idx < 0) idx = -idx;
+      if (idx >= s.S) idx = 2 * (s.S - 1) - idx;
+      v = hann_w(j, s) * wav[(size_t)b * s.S + idx];
+    }
     frames[i] = v;
     mx = fmaxf(mx, fabsf(v));
   }
@@ -136,8 +143,9 @@ void vs_istft_envelope_launch(float* env, const VsStftShape& s, hipStream_t stre
 void vs_stft_basis_launch(float* basis, const VsStftShape& s, float* scale2, hipStream_t stream) {
   hipLaunchKernelGGL(stft_basis_kernel, dim3((s.K * s.win + 255) / 256), dim3(256), 0, stream, basis, s, scale2);
 }
-void vs_stft_frames_launch(const float* wav, float* frames, const VsStftShape& s, unsigned* amax, unsigned grid, hipStream_t stream) {
-  hipLaunchKernelGGL(stft_frames_kernel, dim3(grid), dim3(256), 0, stream, wav, frames, s, amax);
+void vs_stft_frames_launch(const float* wav, float* frames, const VsStftShape& s, unsigned* amax, unsigned grid, hipStream_t stream, int zero_pad) {
+  if (zero_pad) hipLaunchKernelGGL(stft_frames_kernel<true>, dim3(grid), dim3(256), 0, stream, wav, frames, s, amax);
+  else hipLaunchKernelGGL(stft_frames_kernel<false>, dim3(grid), dim3(256), 0, stream, wav, frames, s, amax);
 }
 void vs_spec_to_reim_launch(const float* a, const float* b, const float* phase, float* reim, const VsStftShape& s, unsigned* amax, unsigned grid,
                             hipStream_t stream) {

@@ -64,7 +64,8 @@ int vs_stft_contract(bool split, int layout_w, const float* A, int lda, const fl
 void vs_istft_basis_launch(float* basis, const VsStftShape& s, float* scale2, hipStream_t);
 void vs_istft_envelope_launch(float* env, const VsStftShape& s, hipStream_t);
 void vs_stft_basis_launch(float* basis, const VsStftShape& s, float* scale2, hipStream_t);
-void vs_stft_frames_launch(const float* wav, float* frames, const VsStftShape& s, unsigned* amax, unsigned grid, hipStream_t);
+void vs_stft_frames_launch(const float* wav, float* frames, const VsStftShape& s, unsigned* amax, unsigned grid, hipStream_t,
+                           int zero_pad = 0 /* 1: pad the clip with zeros instead of its reflection */);
 void vs_spec_to_reim_launch(const float* a, const float* b, const float* phase, float* reim, const VsStftShape& s, unsigned* amax, unsigned grid,
                             hipStream_t);
 void vs_overlap_add_launch(const float* frames, const float* env, float* wav, const VsStftShape& s, hipStream_t);

@@ -48,6 +48,7 @@ from glob import glob
 
 import torch
 
+from .config import resolve_audio
 from .trainer import Trainer, load_wav
 
 
@@ -64,7 +65,7 @@ class EvalDataset:
             raise ValueError(" The number of target and mixed Specs and Embs not Match! Check its")
         if not self.emb:
             raise ValueError(f" Test files not found in {test_dir}!")
-        self.sr = int(c.audio[c.audio["backend"]]["sample_rate"])
+        self.sr = int(resolve_audio(c.audio)["sample_rate"])
 
     def __len__(self):
         return len(self.emb)
@@ -78,7 +79,9 @@ def _ragged_batches(c, ds: EvalDataset, device, bs: int):
     """``Trainer.evaluate_ragged``'s batches over the whole set: at most ``bs`` items each, grouped by length."""
     from . import audio
     from .streaming import plan_ragged_batches
-    acfg = c.audio[c.audio["backend"]]
+    acfg = resolve_audio(c.audio)
+    if acfg.get("mel_spec"):
+        raise ValueError("ragged evaluation: forward_ragged takes linear spectrograms; config.audio['mel_spec'] is set")
     hop = int(acfg["hop_length"])
     items = [it for it in (ds[i] for i in range(len(ds))) if it[0].tolist() != [0]]
     for it in items:
@@ -107,7 +110,7 @@ def eval_batches(c, ds: EvalDataset, device, ragged: bool = False):
     order, ``c.test_config['batch_size']`` items each; items whose embedding is [0] are dropped (utils/dataset.py:93-95).
     ragged: ``Trainer.evaluate_ragged``'s batches instead -- items of any length, planned over the whole set."""
     from . import audio
-    acfg = c.audio[c.audio["backend"]]
+    acfg = resolve_audio(c.audio)
     bs = int(c["test_config"]["batch_size"]) if "test_config" in c else 1          # config.json:33-36 (1 when absent)
     if ragged:
         yield from _ragged_batches(c, ds, device, bs)
@@ -175,7 +178,7 @@ def group_speaker_items(items, bs: int):
 def speaker_batches(c, rows, root: str, device):
     """``Trainer.evaluate_speakers``'s batches from the rows of a speakers CSV: (emb, mixed_spec, mixed_phase, target_wavs)."""
     from . import audio
-    acfg = c.audio[c.audio["backend"]]
+    acfg = resolve_audio(c.audio)
     bs = int(c["test_config"]["batch_size"]) if "test_config" in c else 1
     for emb, target_wavs, mixed_wav in group_speaker_items(speaker_items(rows, root, int(acfg["sample_rate"])), bs):
         mixed, phase = audio.wav_to_spec(mixed_wav.to(device), acfg, want_phase=True)

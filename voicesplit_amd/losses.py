@@ -18,13 +18,16 @@ import ctypes
 import torch
 
 from . import _lib
+from .config import resolve_audio
 from .ops import _dev_check, _p, _stream
 
 _WS = {}
 
 
 def loss_dims(B, T, F, audio_cfg) -> "_lib.VsLossDims":
-    """audio_cfg = config.audio[config.audio['backend']] (n_fft, hop_length, win_length, min/ref_level_db)."""
+    """audio_cfg = config.audio[config.audio['backend']] (n_fft, hop_length, win_length, min/ref_level_db); a wavernn or waveglow
+    block gives its geometry (``config.resolve_audio``)."""
+    audio_cfg = resolve_audio(audio_cfg)
     return _lib.VsLossDims(int(B), int(T), int(F), int(audio_cfg["n_fft"]), int(audio_cfg["hop_length"]),
                            int(audio_cfg["win_length"]), float(audio_cfg.get("min_level_db", -100.0)),
                            float(audio_cfg.get("ref_level_db", 20.0)))
@@ -73,6 +76,10 @@ def sisnr_loss(mask, mixed, target, phase, seq_len, audio_cfg, return_wav: bool 
     """loss (0-dim tensor, differentiable w.r.t. ``mask``) of train.py:95-108 for the si_snr loss.
 
     mask, mixed, target, phase: [B, T, num_freq] on the GPU; seq_len: [B] sample counts or None."""
+    audio_cfg = resolve_audio(audio_cfg)
+    if audio_cfg.get("backend", "voicefilter") != "voicefilter":
+        raise ValueError(f"sisnr_loss: the {audio_cfg['backend']} audio back end has no torch_inv_spectrogram in the reference; "
+                         "train it with loss_name 'power_law_compression'")
     B, T, F = mask.shape
     d = loss_dims(B, T, F, audio_cfg)
     return _SiSnr.apply(mask.contiguous(), mixed.contiguous(), target.contiguous(), phase.contiguous(), seq_len, d, return_wav)

@@ -21,6 +21,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .config import resolve_audio
 from .ops import _p, _stream
 
 MIN_CLIP = 1025                       # vs_trim_bounds: the reflect padding of 1024 samples needs y[1024]
@@ -224,6 +225,7 @@ class ClipPool:
         from .speaker import logmel
         ids = [int(i) for i in ids]
         out = torch.zeros(len(ids), encoder.emb_dim, device=self.device)
+        audio_cfg = resolve_audio(audio_cfg)
         min_len = int(audio_cfg["n_fft"]) // 2
         for lo in range(0, len(ids), batch):
             rows = [(k, i) for k, i in enumerate(ids[lo:lo + batch], lo) if self.trimmed_length(i) > min_len]
@@ -363,6 +365,7 @@ class MixtureBatches:
             raise ValueError(f"emb_rows must be 'clip' or 'triplet', got {emb_rows!r}")
         self.pool, self.acfg, self.shard, self.crop, self.seed = pool, audio_cfg, shard, crop, int(seed)
         self.L = samples_for(audio_cfg, audio_len)
+        audio_cfg = resolve_audio(audio_cfg)
         hop = int(audio_cfg["hop_length"])
         if self.L <= 0 or self.L % hop:
             raise ValueError(f"audio_len {audio_len} s = {self.L} samples must be a positive multiple of hop_length {hop}")
@@ -701,6 +704,7 @@ class OverlayBatches:
         self.pool, self.noise_pool, self.acfg, self.shard, self.seed = pool, noise_pool, audio_cfg, shard, int(seed)
         self.drop_last = bool(drop_last)
         self.kinds, self.seconds = tuple(kinds), tuple(seconds)
+        audio_cfg = resolve_audio(audio_cfg)
         self.sr, hop = int(audio_cfg["sample_rate"]), int(audio_cfg["hop_length"])
         if any(int(self.sr * s) % hop for s in self.seconds):
             raise ValueError(f"seconds {self.seconds} at {self.sr} Hz must be multiples of hop_length {hop}")
@@ -937,7 +941,7 @@ def main(argv=None):
     if args.no_overlay != bool(args.noise_csv):
         ap.error("--no-overlay and --noise-csv go together")
     c = load_config(args.config)
-    audio_cfg = c.audio[c.audio["backend"]]
+    audio_cfg = resolve_audio(c.audio)
     form = c.dataset["format"] if "dataset" in c and "format" in c.dataset else None
     encoder = None
     if args.speaker_checkpoint:

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .config import resolve_audio
 from .losses import loss_dims
 from .ops import MATH_CODES, _dev_check, _p, _stream
 
@@ -60,16 +61,17 @@ def mel_to_hz(m):
     return np.where(m >= _MIN_LOG_MEL, log, lin)
 
 
-def mel_band_edges(sr: int, n_mels: int) -> np.ndarray:
-    """The n_mels + 2 band edges in Hz: equally spaced in mel from fmin = 0 to fmax = sr / 2."""
-    return mel_to_hz(np.linspace(hz_to_mel(0.0), hz_to_mel(sr / 2.0), n_mels + 2))
+def mel_band_edges(sr: int, n_mels: int, fmin: float = 0.0, fmax: float = None) -> np.ndarray:
+    """The n_mels + 2 band edges in Hz: equally spaced in mel from fmin (0) to fmax (None: sr / 2)."""
+    return mel_to_hz(np.linspace(hz_to_mel(fmin), hz_to_mel(sr / 2.0 if fmax is None else fmax), n_mels + 2))
 
 
-def mel_filterbank(sr: int, n_fft: int, n_mels: int) -> torch.Tensor:
+def mel_filterbank(sr: int, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: float = None) -> torch.Tensor:
     """[n_mels, n_fft // 2 + 1] float64: triangles on the FFT bin centres between consecutive Slaney band edges, each row scaled
-    by 2 / (f_hi - f_lo) (the "slaney" area norm).  librosa is not a dependency; parity with its own array is not pinned by a test."""
+    by 2 / (f_hi - f_lo) (the "slaney" area norm).  fmin / fmax: librosa.filters.mel's keywords (the wavernn and waveglow blocks
+    set 0 and 8000).  librosa is not a dependency; parity with its own array is not pinned by a test."""
     fft_f = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
-    edges = mel_band_edges(sr, n_mels)
+    edges = mel_band_edges(sr, n_mels, fmin, fmax)
     fdiff = np.diff(edges)
     ramps = edges[:, None] - fft_f[None, :]
     lower = -ramps[:-2] / fdiff[:-1, None]
@@ -95,6 +97,7 @@ def logmel(wav: torch.Tensor, audio_cfg, num_mels: int = 40) -> torch.Tensor:
     if wav.dim() != 1:
         raise ValueError(f"wav: expected one clip [n], got {tuple(wav.shape)}")
     n = wav.numel()
+    audio_cfg = resolve_audio(audio_cfg)
     n_fft, hop = int(audio_cfg["n_fft"]), int(audio_cfg["hop_length"])
     d = loss_dims(1, 1 + n // hop, n_fft // 2 + 1, audio_cfg)
     nbytes = lib.vs_logmel_workspace_bytes(ctypes.byref(d), n, int(num_mels))
@@ -273,6 +276,7 @@ def embed_directory(encoder, data_dir: str, audio_cfg, batch: int = 64, device="
     mel_fn = mel_fn or (lambda w: logmel(w, audio_cfg, encoder.num_mels))
     files = sorted(glob.glob(os.path.join(data_dir, "*" + REF_WAV_SUFFIX)))
     sr = int(audio_cfg.get("sample_rate", 16000))
+    audio_cfg = resolve_audio(audio_cfg)
     min_len = int(audio_cfg["n_fft"]) // 2
     good = 0
     for i in range(0, len(files), batch):
@@ -331,7 +335,7 @@ def main(argv=None):
                     "linear gain with a -2 dB peak cap, not ffmpeg's dynamic loudnorm)")
     args = ap.parse_args(argv)
     c = load_config(args.config) if args.config else default_config()
-    audio_cfg = c.audio[c.audio["backend"]]
+    audio_cfg = resolve_audio(c.audio)
     enc = SpeakerEncoder(num_mels=int(audio_cfg.get("num_mels", 40)))
     enc.load_state_dict(torch.load(args.checkpoint, map_location="cpu"), strict=True)
     enc = enc.eval().to(args.device)

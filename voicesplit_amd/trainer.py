@@ -32,6 +32,7 @@ from typing import Callable, Iterable, Iterator, List, Optional, Sequence
 
 import torch
 
+from .config import resolve_audio
 from .sharding import GradientBucket, sync_buffers
 
 
@@ -85,7 +86,7 @@ def make_criterion(c) -> Callable:
     from . import losses
     name = c.loss["loss_name"]
     if name == "si_snr":
-        audio_cfg = c.audio[c.audio["backend"]]
+        audio_cfg = resolve_audio(c.audio)
         return lambda mask, mixed, target, seq_len, phase: losses.sisnr_loss(mask, mixed, target, phase, seq_len, audio_cfg)
     if name == "power_law_compression":
         power, ratio = c.loss["power"], c.loss["complex_loss_ratio"]
@@ -395,7 +396,7 @@ class Trainer:
         the [B, S] target waveform, S = hop * (T - 1)."""
         from . import audio, metrics
         self.model.eval()
-        acfg = self.c.audio[self.c.audio["backend"]]
+        acfg = resolve_audio(self.c.audio)
         tot, cnt = 0.0, 0
         dev = self.device
         sdr_acc = torch.zeros(2, dtype=torch.float64, device=dev)          # (sum of SDRs, rows scored), on the device
@@ -435,7 +436,7 @@ class Trainer:
         target_wavs a list of 1-D host waveforms, frames the items' own frame counts."""
         from . import audio, metrics
         self.model.eval()
-        acfg = self.c.audio[self.c.audio["backend"]]
+        acfg = resolve_audio(self.c.audio)
         dev = self.device
         tot, cnt = 0.0, 0
         sdr_acc = torch.zeros(2, dtype=torch.float64, device=dev)
@@ -471,7 +472,7 @@ class Trainer:
         removed) are skipped and counted in ``skipped``; NaN means when none is scored."""
         from . import audio, metrics
         self.model.eval()
-        acfg = self.c.audio[self.c.audio["backend"]]
+        acfg = resolve_audio(self.c.audio)
         sr = int(acfg["sample_rate"])
         dev = self.device
         acc = torch.zeros(4, dtype=torch.float64, device=dev)      # sum of STOI, of ESTOI; rows scored, skipped
@@ -531,7 +532,7 @@ class Trainer:
         speaker k over the rows it can score (status 0), whatever ``bss_eval`` said of the item."""
         from . import audio, metrics
         self.model.eval()
-        acfg = self.c.audio[self.c.audio["backend"]]
+        acfg = resolve_audio(self.c.audio)
         dev = self.device
         acc = torch.zeros(6, dtype=torch.float64, device=dev)      # sums of sdr, sir, sar; sources, items scored; items confused
         acc_i = torch.zeros(3, dtype=torch.float64, device=dev)    # sums of STOI, ESTOI; rows scored
@@ -697,7 +698,7 @@ class SpecWavDataset:
             raise ValueError(" The number of target and mixed Specs and Embs not Match! Check its")
         if not self.emb:
             raise ValueError(" Training files not found !")
-        self.sr = int(c.audio[c.audio["backend"]]["sample_rate"])
+        self.sr = int(resolve_audio(c.audio)["sample_rate"])
 
     def __len__(self):
         return len(self.emb)
@@ -720,7 +721,7 @@ class SpecWavDataset:
         wav = torch.stack([it[2] for it in items]).to(device)
         seq_len = torch.stack([it[3] for it in items]).reshape(-1).to(device)
         target_wav = torch.stack([it[4] for it in items])
-        mixed, phase = audio.wav_to_spec(wav, self.c.audio[self.c.audio["backend"]], want_phase=True)
+        mixed, phase = audio.wav_to_spec(wav, resolve_audio(self.c.audio), want_phase=True)
         return emb, target, mixed, seq_len, target_wav, phase
 
 
@@ -755,7 +756,7 @@ class BatchFeeder:
         self.prefetch_factor = prefetch_factor
         self.cuda = self.device.type == "cuda"
         self._copy = torch.cuda.Stream(self.device) if self.cuda else None
-        self.acfg = dataset.c.audio[dataset.c.audio["backend"]]
+        self.acfg = resolve_audio(dataset.c.audio)
 
     def host_batches(self, epoch: int, chain: int = 1):
         """The DataLoader of one epoch: host tuples (``host_collate``) in ``EpochShard`` order.  chain > 1: the index batches of
@@ -953,7 +954,7 @@ def main(argv=None):
     log_dir = os.path.join(c.train_config["logs_path"], c.model_name)      # train.py:154
     if rank == 0:
         os.makedirs(log_dir, exist_ok=True)
-    acfg = c.audio[c.audio["backend"]]
+    acfg = resolve_audio(c.audio)
     b = c.train_config["batch_size"]
     if args.synthetic_steps:
         T = 1 + (int(c.audio["audio_len"]) * acfg["sample_rate"]) // acfg["hop_length"]
