@@ -134,7 +134,7 @@ def _bptt_fp64(gates, c, dout, w_hh):
 
 
 def test_b64_train_backward_bf16_stagewise_vs_fp64_on_the_tapes_operands():
-    from voicesplit_amd import _lib, ops
+    from voicesplit_amd import _call, _lib, ops
     m, sd, dims_d = _model(5, 6.0)
     m.train()
     B, T, Fq, H = 64, 301, 601, dims_d["lstm_dim"]
@@ -310,8 +310,8 @@ def test_b64_train_backward_bf16_stagewise_vs_fp64_on_the_tapes_operands():
             else:
                 ones, zeros = torch.ones(64, device="cuda"), torch.zeros(64, device="cuda")
                 da1 = torch.empty_like(dz)
-                _lib.check(lib.vs_nhwc_conv(ops._p(dz), ops._p(packed), ops._p(ones), ops._p(zeros), ops._p(da1), B, T, Fq, KT, KF, dil,
-                                            _lib.ACT_NONE, ops._p(None), ops._stream()), "vs_nhwc_conv")
+                _lib.check(lib.vs_nhwc_conv(_call.ptr(dz), _call.ptr(packed), _call.ptr(ones), _call.ptr(zeros), _call.ptr(da1), B, T, Fq, KT, KF, dil,
+                                            _lib.ACT_NONE, _call.ptr(None), _call.stream()), "vs_nhwc_conv")
                 for b0, da in _conv_full_fp64(dz, wt, dil):
                     _bf16_close(da1[b0:b0 + da.shape[0]], da, ("da1", b0), floor=3e-5)
                     del da

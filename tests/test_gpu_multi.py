@@ -117,7 +117,7 @@ def _stages(m, sd, x, dvecs, act, lengths=None):
     B, T, K = x.shape[0], x.shape[1], dvecs.shape[1]
     dims = _dims(B, T)
     xc, dc = x.cuda(), dvecs.cuda()
-    feat = ops.conv_stack(sdc, xc, dims, act) if lengths is None else ops.conv_stack_ragged(sdc, xc, lengths, dims, act)
+    feat = ops.conv_stack(sdc, xc, dims, act, lengths=lengths)
     lo = ops.bilstm_multi(sdc, feat, dc, dims, lengths=lengths)
     _, logits = ops.head(sdc, lo.view(B * K, T, -1), _dims(B * K, T), want_logits=True)
     with torch.no_grad():

@@ -70,8 +70,8 @@ def _stages(m, sd, x, dvec, lengths, act):
     d = R.default_dims()
     dims = ops.make_dims(x.shape[0], x.shape[1], d["num_freq"], d["emb_dim"], d["lstm_dim"], d["fc1_dim"], d["fc2_dim"])
     xc, dc = x.cuda(), dvec.cuda()
-    feat = ops.conv_stack_ragged(sdc, xc, lengths, dims, act)
-    lo = ops.bilstm_ragged(sdc, feat, dc, lengths, dims)
+    feat = ops.conv_stack(sdc, xc, dims, act, lengths=lengths)
+    lo = ops.bilstm(sdc, feat, dc, dims, lengths=lengths)
     _, logits = ops.head(sdc, lo, dims, want_logits=True)
     with torch.no_grad():
         mask = m.forward_ragged(xc, dc, lengths)
@@ -229,10 +229,10 @@ def test_refusals():
         assert lib.vs_set_lstm_kernel(mode) == 0
         try:
             with pytest.raises(VoiceSplitHipError, match="per-item lengths"):
-                ops.bilstm_ragged(sdc, feat, dc, lengths, dims)
+                ops.bilstm(sdc, feat, dc, dims, lengths=lengths)
         finally:
             assert lib.vs_set_lstm_kernel(0) == 0
-    assert torch.isfinite(ops.bilstm_ragged(sdc, feat, dc, lengths, dims)).all()
+    assert torch.isfinite(ops.bilstm(sdc, feat, dc, dims, lengths=lengths)).all()
 
 
 def _demo_clips():

@@ -180,12 +180,12 @@ class _StubLib:
 
 @pytest.fixture
 def stub(monkeypatch):
-    from voicesplit_amd import audio
+    from voicesplit_amd import _call
     lib = _StubLib()
-    monkeypatch.setattr(audio._lib, "load", lambda path=None: lib)
-    monkeypatch.setattr(audio, "_dev_check", lambda t, name, dtype=torch.float32: None)
-    monkeypatch.setattr(audio, "_stream", lambda: None)
-    monkeypatch.setattr(audio, "_WS", {})
+    monkeypatch.setattr(_call._lib, "load", lambda path=None: lib)
+    monkeypatch.setattr(_call, "dev_check", lambda t, name, dtype=torch.float32: None)
+    monkeypatch.setattr(_call, "stream", lambda: None)
+    monkeypatch.setattr(_call, "_SCRATCH", {})
     monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
     return lib
 

@@ -93,7 +93,8 @@ def test_module_surface():
     assert inspect.signature(ops.forward_prepared).parameters["lengths"].default is None
     assert inspect.signature(evaluate.eval_batches).parameters["ragged"].default is False
     assert callable(audio.separate_many) and callable(Trainer.evaluate_ragged)
-    assert callable(ops.conv_stack_ragged) and callable(ops.bilstm_ragged)
+    assert inspect.signature(ops.conv_stack).parameters["lengths"].default is None
+    assert inspect.signature(ops.bilstm).parameters["lengths"].default is None
 
 
 def test_lengths_are_range_checked_on_the_host():

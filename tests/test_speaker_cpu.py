@@ -58,8 +58,8 @@ def test_short_clip_and_ragged_offsets():
 
 
 def test_forward_refuses_a_clip_shorter_than_one_window(monkeypatch):
-    from voicesplit_amd import SpeakerEncoder, speaker
-    monkeypatch.setattr(speaker, "_dev_check", lambda *a, **k: None)      # no device here: only the length check is exercised
+    from voicesplit_amd import SpeakerEncoder, _call
+    monkeypatch.setattr(_call, "dev_check", lambda *a, **k: None)         # no device here: only the length check is exercised
     with pytest.raises(ValueError, match="fewer than one window"):
         SpeakerEncoder()(torch.zeros(40, 79))
 

@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
-from voicesplit_amd import _lib, ops  # noqa: E402
+from voicesplit_amd import _call, _lib, ops  # noqa: E402
 
 
 def main():
@@ -29,23 +29,23 @@ def main():
             continue
         w = (torch.randn(64, 64, KT, KF, generator=g) / (64 * KT * KF) ** 0.5).to(dev)
         packed = torch.empty(lib.vs_conv64_packed_floats(KT, KF), dtype=torch.float32, device=dev)
-        _lib.check(lib.vs_conv64_pack(ops._p(w), ops._p(packed), KT, KF, ops._stream()), "pack")
+        _lib.check(lib.vs_conv64_pack(_call.ptr(w), _call.ptr(packed), KT, KF, _call.stream()), "pack")
         packed16 = torch.empty(lib.vs_conv64_packed_f16_floats(KT, KF), dtype=torch.float32, device=dev)
         scales = torch.zeros(8, dtype=torch.float32, device=dev)
         amax = scales[4:].view(torch.int32)
-        _lib.check(lib.vs_pow2_scale(ops._p(x), x.numel(), ops._p(amax), ops._p(scales), ops._stream()), "scale")
-        _lib.check(lib.vs_conv64_pack_f16(ops._p(w), ops._p(packed16), KT, KF, 0, ops._p(amax[1:]), ops._p(scales[2:]), ops._stream()), "pack16")
+        _lib.check(lib.vs_pow2_scale(_call.ptr(x), x.numel(), _call.ptr(amax), _call.ptr(scales), _call.stream()), "scale")
+        _lib.check(lib.vs_conv64_pack_f16(_call.ptr(w), _call.ptr(packed16), KT, KF, 0, _call.ptr(amax[1:]), _call.ptr(scales[2:]), _call.stream()), "pack16")
         for act in (("mish_f16x3",) if only else ("mish", "none", "mish_f16x3", "scale_pass")):
             def run():
                 if act == "scale_pass":
-                    _lib.check(lib.vs_pow2_scale(ops._p(x), x.numel(), ops._p(amax), ops._p(scales), ops._stream()), "scale")
+                    _lib.check(lib.vs_pow2_scale(_call.ptr(x), x.numel(), _call.ptr(amax), _call.ptr(scales), _call.stream()), "scale")
                 elif act == "mish_f16x3":
-                    _lib.check(lib.vs_conv64_f16x3_fwd(ops._p(x), ops._p(packed16), ops._p(scale), ops._p(shift), ops._p(scales),
-                                                       ops._p(scales[2:]), ops._p(out), B, T, F, KT, KF, dil,
-                                                       ops.ACT_CODES["mish"], ops._stream()), "conv16")
+                    _lib.check(lib.vs_conv64_f16x3_fwd(_call.ptr(x), _call.ptr(packed16), _call.ptr(scale), _call.ptr(shift), _call.ptr(scales),
+                                                       _call.ptr(scales[2:]), _call.ptr(out), B, T, F, KT, KF, dil,
+                                                       ops.ACT_CODES["mish"], _call.stream()), "conv16")
                 else:
-                    _lib.check(lib.vs_conv64_fwd(ops._p(x), ops._p(packed), ops._p(scale), ops._p(shift), ops._p(out),
-                                                 B, T, F, KT, KF, dil, ops.ACT_CODES[act], ops._stream()), "conv")
+                    _lib.check(lib.vs_conv64_fwd(_call.ptr(x), _call.ptr(packed), _call.ptr(scale), _call.ptr(shift), _call.ptr(out),
+                                                 B, T, F, KT, KF, dil, ops.ACT_CODES[act], _call.stream()), "conv")
             run()
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -37,7 +37,7 @@ def main():
     import torch
     from mix_time import _event_ms, _stats
     from voicesplit_amd import _lib, loudness
-    from voicesplit_amd.ops import _p, _stream
+    from voicesplit_amd._call import ptr as _p, stream as _stream
     if not torch.cuda.is_available():
         raise SystemExit("loudness_time.py measures the GPU: no device here")
     dev = torch.device("cuda:0")

@@ -42,10 +42,7 @@ def main():
     ap.add_argument("--block-ms", type=float, default=300.0)
     args = ap.parse_args()
     import voicesplit_amd as V
-    from voicesplit_amd import _lib
-    from voicesplit_amd.ops import _p, _stream
-    from voicesplit_amd.speaker import _workspace
-    lib = _lib.load()
+    from voicesplit_amd import _call
     dev = "cuda:0"
     torch.manual_seed(0)
     enc = V.SpeakerEncoder().eval().to(dev)
@@ -64,13 +61,12 @@ def main():
         frames = [u * T for u in range(U + 1)]
         wins = [u * (N // U) for u in range(U + 1)]
         offs = torch.tensor([frames, wins], dtype=torch.int32, device=dev)
-        ws = _workspace(lib.vs_speaker_workspace_bytes(ctypes.byref(d), N, U * T), dev, "embed")
+        ws = _call.scratch("embed", _call.sized("speaker_workspace_bytes", ctypes.byref(d), N, U * T), dev)
         h_last = torch.empty(N, 768, device=dev)
 
         def rec():
-            rc = lib.vs_speaker_embed(ctypes.byref(d), _p(prepared), prepared.numel(), _p(mel), U * T, _p(offs[0]), _p(offs[1]), U, N,
-                                      _p(h_last), None, None, _p(ws), ws.numel(), _stream())
-            assert rc == 0, lib.vs_last_error()
+            _call.call("speaker_embed", dev, ctypes.byref(d), prepared, prepared.numel(), mel, U * T, offs[0], offs[1], U, N,
+                       h_last, None, None, ws, ws.numel())
 
         def e2e():
             enc.embed_many([V.logmel(w, AUDIO) for w in wavs])

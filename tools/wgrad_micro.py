@@ -7,7 +7,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
-from voicesplit_amd import _lib, ops  # noqa: E402
+from voicesplit_amd import _call, _lib  # noqa: E402
 
 
 def main():
@@ -26,9 +26,9 @@ def main():
         for math in ("fp32", "f16x3"):
             def run():
                 if math == "fp32":
-                    _lib.check(lib.vs_conv64_wgrad(ops._p(dz), ops._p(x), ops._p(part), ops._p(dw), B, T, F, KT, KF, dil, ops._stream()), "wgrad")
+                    _lib.check(lib.vs_conv64_wgrad(_call.ptr(dz), _call.ptr(x), _call.ptr(part), _call.ptr(dw), B, T, F, KT, KF, dil, _call.stream()), "wgrad")
                 else:
-                    _lib.check(lib.vs_conv64_wgrad_f16x3(ops._p(dz), ops._p(x), ops._p(part), ops._p(dw), ops._p(scratch), B, T, F, KT, KF, dil, ops._stream()), "wgrad16")
+                    _lib.check(lib.vs_conv64_wgrad_f16x3(_call.ptr(dz), _call.ptr(x), _call.ptr(part), _call.ptr(dw), _call.ptr(scratch), B, T, F, KT, KF, dil, _call.stream()), "wgrad16")
             run()
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -19,26 +19,9 @@ import torch
 
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 from .config import resolve_audio as resolve
 from .losses import loss_dims
-from .ops import _dev_check, _p, _stream
-
-_WS = {}
-
-
-def _workspace(d, device, sizer="vs_audio_workspace_bytes"):
-    lib = _lib.load()
-    n = getattr(lib, sizer)(ctypes.byref(d))
-    if n == 0:
-        _lib.check(-1, sizer)
-    key = torch.device(device).index
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        _WS.pop(key, None)
-        ws = torch.empty(n, dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
 
 
 def frames_for(n_samples: int, hop: int) -> int:
@@ -51,20 +34,17 @@ def wav_to_spec(wav: torch.Tensor, audio_cfg, want_phase: bool = True):
     audio_cfg = resolve(audio_cfg)
     if _foreign(audio_cfg):
         return _codec_wav_to_spec(wav, audio_cfg, want_phase, bool(audio_cfg["mel_spec"]))
-    lib = _lib.load()
-    _dev_check(wav, "wav")
+    _call.dev_check(wav, "wav")
     B, S = wav.shape
     hop = int(audio_cfg["hop_length"])
     if S % hop:
         raise ValueError(f"wav length {S} must be a multiple of hop_length {hop} (crop or pad the clip)")
     T, F = S // hop + 1, int(audio_cfg["n_fft"]) // 2 + 1
     d = loss_dims(B, T, F, audio_cfg)
-    ws = _workspace(d, wav.device)
+    ws = _call.scratch("audio", _call.sized("audio_workspace_bytes", ctypes.byref(d)), wav.device)
     spec = torch.empty(B, T, F, device=wav.device)
     phase = torch.empty(B, T, F, device=wav.device) if want_phase else None
-    with torch.cuda.device(wav.device):
-        rc = lib.vs_wav_to_spec(ctypes.byref(d), _p(wav), _p(spec), _p(phase), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_wav_to_spec")
+    _call.call("wav_to_spec", wav.device, ctypes.byref(d), wav, spec, phase, ws, ws.numel())
     return spec, phase
 
 
@@ -84,18 +64,15 @@ def spec_to_wav(spec: torch.Tensor, phase: torch.Tensor = None, audio_cfg=None, 
         return griffin_lim(spec, audio_cfg, mask=mask, generator=generator)
     if _foreign(audio_cfg):
         return _deemphasised(mag_to_wav(_linear_target(spec, audio_cfg, mask), phase, audio_cfg), audio_cfg)
-    lib = _lib.load()
     for n, t in (("spec", spec), ("phase", phase)):
-        _dev_check(t, n)
+        _call.dev_check(t, n)
     if mask is not None:
-        _dev_check(mask, "mask")
+        _call.dev_check(mask, "mask")
     B, T, F = spec.shape
     d = loss_dims(B, T, F, audio_cfg)
-    ws = _workspace(d, spec.device)
+    ws = _call.scratch("audio", _call.sized("audio_workspace_bytes", ctypes.byref(d)), spec.device)
     wav = torch.empty(B, d.hop * (T - 1), device=spec.device)
-    with torch.cuda.device(spec.device):
-        rc = lib.vs_spec_to_wav(ctypes.byref(d), _p(spec), _p(mask), _p(phase), _p(wav), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_spec_to_wav")
+    _call.call("spec_to_wav", spec.device, ctypes.byref(d), spec, mask, phase, wav, ws, ws.numel())
     return wav
 
 
@@ -113,26 +90,22 @@ def griffin_lim(spec: torch.Tensor, audio_cfg, n_iter: int = None, power: float 
         out = griffin_lim_mag(_linear_target(spec, audio_cfg, mask), audio_cfg, n_iter=n_iter, power=power, init_phase=init_phase,
                               generator=generator, return_residual=return_residual)
         return (_deemphasised(out[0], audio_cfg), out[1]) if return_residual else _deemphasised(out, audio_cfg)
-    lib = _lib.load()
-    _dev_check(spec, "spec")
+    _call.dev_check(spec, "spec")
     if mask is not None:
-        _dev_check(mask, "mask")
+        _call.dev_check(mask, "mask")
     n_iter = int(audio_cfg["griffin_lim_iters"] if n_iter is None else n_iter)
     power = float(audio_cfg["power"] if power is None else power)
     if init_phase is None:
         init_phase = 2.0 * math.pi * torch.rand(spec.shape, device=spec.device, dtype=torch.float32, generator=generator)
-    _dev_check(init_phase, "init_phase")
+    _call.dev_check(init_phase, "init_phase")
     if init_phase.shape != spec.shape or (mask is not None and mask.shape != spec.shape):
         raise ValueError(f"init_phase / mask must have the shape of spec {tuple(spec.shape)}")
     B, T, F = spec.shape
     d = loss_dims(B, T, F, audio_cfg)
-    ws = _workspace(d, spec.device, "vs_griffin_lim_workspace_bytes")
+    ws = _call.scratch("audio", _call.sized("griffin_lim_workspace_bytes", ctypes.byref(d)), spec.device)
     wav = torch.empty(B, d.hop * (T - 1), device=spec.device)
     res = torch.empty(max(n_iter, 0), B, dtype=torch.float64, device=spec.device) if return_residual else None
-    with torch.cuda.device(spec.device):
-        rc = lib.vs_griffin_lim(ctypes.byref(d), _p(spec), _p(mask), _p(init_phase), power, n_iter, _p(wav), _p(res),
-                                _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_griffin_lim")
+    _call.call("griffin_lim", spec.device, ctypes.byref(d), spec, mask, init_phase, power, n_iter, wav, res, ws, ws.numel())
     return (wav, res) if return_residual else wav
 
 
@@ -196,43 +169,34 @@ def _mel(audio_cfg, device):
 def decode(spec: torch.Tensor, audio_cfg, mask: torch.Tensor = None) -> torch.Tensor:
     """Stored values (times mask) -> linear fp32 magnitudes of the same shape, under the block's codec; evaluated in fp64 on the
     device and rounded once."""
-    lib = _lib.load()
-    _dev_check(spec, "spec")
+    _call.dev_check(spec, "spec")
     if mask is not None:
-        _dev_check(mask, "mask")
+        _call.dev_check(mask, "mask")
         if mask.shape != spec.shape:
             raise ValueError(f"mask must have the shape of spec {tuple(spec.shape)}")
     c = _codec_struct(codec_of(audio_cfg))
     out = torch.empty_like(spec)
-    with torch.cuda.device(spec.device):
-        rc = lib.vs_codec_decode(ctypes.byref(c), _p(spec), _p(mask), spec.numel(), _p(out), _stream())
-    _lib.check(rc, "vs_codec_decode")
+    _call.call("codec_decode", spec.device, ctypes.byref(c), spec, mask, spec.numel(), out)
     return out
 
 
 def encode(mag: torch.Tensor, audio_cfg) -> torch.Tensor:
     """Linear magnitudes -> stored values of the block's codec (``max(floor, .)`` first)."""
-    lib = _lib.load()
-    _dev_check(mag, "mag")
+    _call.dev_check(mag, "mag")
     c = _codec_struct(codec_of(audio_cfg))
     out = torch.empty_like(mag)
-    with torch.cuda.device(mag.device):
-        rc = lib.vs_codec_encode(ctypes.byref(c), _p(mag), mag.numel(), _p(out), _stream())
-    _lib.check(rc, "vs_codec_encode")
+    _call.call("codec_encode", mag.device, ctypes.byref(c), mag, mag.numel(), out)
     return out
 
 
 def project(x: torch.Tensor, w: torch.Tensor, floor: float = 0.0) -> torch.Tensor:
     """``max(floor, x @ w.T)``: x [..., K], w [N, K] -> [..., N], one fp32 FMA chain per output in the order of K."""
-    lib = _lib.load()
-    _dev_check(x, "x")
-    _dev_check(w, "w")
+    _call.dev_check(x, "x")
+    _call.dev_check(w, "w")
     if w.dim() != 2 or x.shape[-1] != w.shape[1]:
         raise ValueError(f"project: x {tuple(x.shape)} against w {tuple(w.shape)}")
     out = torch.empty(*x.shape[:-1], w.shape[0], device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.vs_project_floor(_p(x), _p(w), _p(out), x.numel() // x.shape[-1], w.shape[0], w.shape[1], float(floor), _stream())
-    _lib.check(rc, "vs_project_floor")
+    _call.call("project_floor", x.device, x, w, out, x.numel() // x.shape[-1], w.shape[0], w.shape[1], float(floor))
     return out
 
 
@@ -253,8 +217,7 @@ def _deemphasised(wav, cfg):
 
 
 def _codec_wav_to_spec(wav, cfg, want_phase, mel):
-    lib = _lib.load()
-    _dev_check(wav, "wav")
+    _call.dev_check(wav, "wav")
     B, S = wav.shape
     hop = int(cfg["hop_length"])
     if S % hop:
@@ -262,15 +225,12 @@ def _codec_wav_to_spec(wav, cfg, want_phase, mel):
     T, F = S // hop + 1, int(cfg["n_fft"]) // 2 + 1
     d = loss_dims(B, T, F, cfg)
     c = _codec_struct(codec_of(cfg))
-    ws = _workspace(d, wav.device)
+    ws = _call.scratch("audio", _call.sized("audio_workspace_bytes", ctypes.byref(d)), wav.device)
     basis = mel_basis(cfg, wav.device) if mel else None
     n_mels = int(basis.shape[0]) if mel else 0
     spec = torch.empty(B, T, n_mels if mel else F, device=wav.device)
     phase = torch.empty(B, T, F, device=wav.device) if want_phase else None
-    with torch.cuda.device(wav.device):
-        rc = lib.vs_codec_wav_to_spec(ctypes.byref(d), ctypes.byref(c), _p(wav), _p(basis), n_mels, _p(spec), _p(phase), _p(ws),
-                                      ws.numel(), _stream())
-    _lib.check(rc, "vs_codec_wav_to_spec")
+    _call.call("codec_wav_to_spec", wav.device, ctypes.byref(d), ctypes.byref(c), wav, basis, n_mels, spec, phase, ws, ws.numel())
     return spec, phase
 
 
@@ -284,18 +244,15 @@ def wav_to_mel(wav: torch.Tensor, audio_cfg):
 
 def mag_to_wav(mag: torch.Tensor, phase: torch.Tensor, audio_cfg) -> torch.Tensor:
     """A LINEAR magnitude and a phase [B,T,F] -> wav [B, hop*(T-1)]: ``spec_to_wav`` behind its decoder (no de-emphasis)."""
-    lib = _lib.load()
     for n, t in (("mag", mag), ("phase", phase)):
-        _dev_check(t, n)
+        _call.dev_check(t, n)
     if phase.shape != mag.shape:
         raise ValueError(f"phase must have the shape of mag {tuple(mag.shape)}")
     B, T, F = mag.shape
     d = loss_dims(B, T, F, audio_cfg)
-    ws = _workspace(d, mag.device)
+    ws = _call.scratch("audio", _call.sized("audio_workspace_bytes", ctypes.byref(d)), mag.device)
     wav = torch.empty(B, d.hop * (T - 1), device=mag.device)
-    with torch.cuda.device(mag.device):
-        rc = lib.vs_mag_to_wav(ctypes.byref(d), _p(mag), _p(phase), _p(wav), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_mag_to_wav")
+    _call.call("mag_to_wav", mag.device, ctypes.byref(d), mag, phase, wav, ws, ws.numel())
     return wav
 
 
@@ -304,9 +261,8 @@ def griffin_lim_mag(mag: torch.Tensor, audio_cfg, n_iter: int = None, power: flo
     """``_griffin_lim(mag ** power)`` on a LINEAR magnitude [B,T,F] -> wav [B, hop*(T-1)] (no de-emphasis).  pad: "reflect" or "zero",
     the padding of the inner transform (None: the block's own: zeros for waveglow, utils/audio_processor.py:411-418).  The other
     arguments as in ``griffin_lim``."""
-    lib = _lib.load()
     cfg = resolve(audio_cfg)
-    _dev_check(mag, "mag")
+    _call.dev_check(mag, "mag")
     n_iter = int(cfg["griffin_lim_iters"] if n_iter is None else n_iter)
     power = float(cfg["power"] if power is None else power)
     pad = codec_of(cfg)["gl_pad"] if pad is None else pad
@@ -314,22 +270,16 @@ def griffin_lim_mag(mag: torch.Tensor, audio_cfg, n_iter: int = None, power: flo
         raise ValueError(f"griffin_lim_mag: pad {pad!r} is not one of {tuple(_PADS)}")
     if init_phase is None:
         init_phase = 2.0 * math.pi * torch.rand(mag.shape, device=mag.device, dtype=torch.float32, generator=generator)
-    _dev_check(init_phase, "init_phase")
+    _call.dev_check(init_phase, "init_phase")
     if init_phase.shape != mag.shape:
         raise ValueError(f"init_phase must have the shape of mag {tuple(mag.shape)}")
     B, T, F = mag.shape
     d = loss_dims(B, T, F, cfg)
-    ws = _workspace(d, mag.device, "vs_griffin_lim_workspace_bytes")
+    ws = _call.scratch("audio", _call.sized("griffin_lim_workspace_bytes", ctypes.byref(d)), mag.device)
     wav = torch.empty(B, d.hop * (T - 1), device=mag.device)
     res = torch.empty(max(n_iter, 0), B, dtype=torch.float64, device=mag.device) if return_residual else None
-    with torch.cuda.device(mag.device):
-        rc = lib.vs_griffin_lim_mag(ctypes.byref(d), _p(mag), _p(init_phase), power, n_iter, _PADS[pad], _p(wav), _p(res),
-                                    _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_griffin_lim_mag")
+    _call.call("griffin_lim_mag", mag.device, ctypes.byref(d), mag, init_phase, power, n_iter, _PADS[pad], wav, res, ws, ws.numel())
     return (wav, res) if return_residual else wav
-
-
-_DE_WS = {}
 
 
 def deemphasis_block() -> int:
@@ -346,34 +296,22 @@ def _rows(wav):
 def deemphasis(wav: torch.Tensor, coef: float) -> torch.Tensor:
     """y[n] = wav[n] + coef * y[n-1], y[-1] = 0 (``scipy.signal.lfilter([1], [1, -coef], wav)``, apply_inv_preemphasis) on wav [n] or
     [B, n]: a two-sweep scan in fp64 (vs_deemphasis); a row's bits do not depend on the batch around it."""
-    lib = _lib.load()
-    _dev_check(wav, "wav")
+    _call.dev_check(wav, "wav")
     x = _rows(wav)
     B, N = x.shape
-    n = lib.vs_deemphasis_workspace_bytes(B, N)
-    if n == 0:
-        _lib.check(-1, "vs_deemphasis_workspace_bytes")
-    key = torch.device(wav.device).index
-    ws = _DE_WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _DE_WS[key] = torch.empty(n, dtype=torch.uint8, device=wav.device)
+    ws = _call.scratch("deemph", _call.sized("deemphasis_workspace_bytes", B, N), wav.device)
     y = torch.empty_like(wav)
-    with torch.cuda.device(wav.device):
-        rc = lib.vs_deemphasis(_p(x), _p(y), B, N, float(coef), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_deemphasis")
+    _call.call("deemphasis", wav.device, x, y, B, N, float(coef), ws, ws.numel())
     return y
 
 
 def preemphasis(wav: torch.Tensor, coef: float) -> torch.Tensor:
     """y[n] = wav[n] - coef * wav[n-1], wav[-1] = 0 (``lfilter([1, -coef], [1], wav)``, apply_preemphasis) on wav [n] or [B, n]; the
     difference in fp64, rounded once.  (The front end forms it inside its framing gather; this is the stand-alone filter.)"""
-    lib = _lib.load()
-    _dev_check(wav, "wav")
+    _call.dev_check(wav, "wav")
     x = _rows(wav)
     y = torch.empty_like(wav)
-    with torch.cuda.device(wav.device):
-        rc = lib.vs_preemphasis(_p(x), _p(y), x.shape[0], x.shape[1], float(coef), _stream())
-    _lib.check(rc, "vs_preemphasis")
+    _call.call("preemphasis", wav.device, x, y, x.shape[0], x.shape[1], float(coef))
     return y
 
 

@@ -17,11 +17,8 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _call, _lib
 from .config import resolve_audio
-from .ops import _dev_check, _p, _stream
-
-_WS = {}
 
 
 def loss_dims(B, T, F, audio_cfg) -> "_lib.VsLossDims":
@@ -33,36 +30,19 @@ def loss_dims(B, T, F, audio_cfg) -> "_lib.VsLossDims":
                            float(audio_cfg.get("ref_level_db", 20.0)))
 
 
-def _workspace(d, device):
-    lib = _lib.load()
-    n = lib.vs_sisnr_workspace_bytes(ctypes.byref(d))
-    if n == 0:
-        _lib.check(-1, "vs_sisnr_workspace_bytes")
-    key = torch.device(device).index
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        _WS.pop(key, None)
-        ws = torch.empty(n, dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
-
-
 class _SiSnr(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mask, mixed, target, phase, seq_len, d, want_wav):
-        lib = _lib.load()
         for n, t in (("mask", mask), ("mixed", mixed), ("target", target), ("phase", phase)):
-            _dev_check(t.detach(), n)
+            _call.dev_check(t.detach(), n)
         if seq_len is not None:
             seq_len = seq_len.to(device=mask.device, dtype=torch.int32).contiguous()
-        ws = _workspace(d, mask.device)
+        ws = _call.scratch("loss", _call.sized("sisnr_workspace_bytes", ctypes.byref(d)), mask.device)
         loss = torch.empty((), dtype=torch.float32, device=mask.device)
         dmask = torch.empty_like(mask) if ctx.needs_input_grad[0] else None
         wav = torch.empty(d.B, d.hop * (d.T - 1), device=mask.device) if want_wav else None
-        with torch.cuda.device(mask.device):
-            rc = lib.vs_sisnr_loss(ctypes.byref(d), _p(mixed), _p(mask.detach()), _p(target), _p(phase), _p(seq_len), _p(ws),
-                                   ws.numel(), _p(loss), _p(dmask), _p(wav), _stream())
-        _lib.check(rc, "vs_sisnr_loss")
+        _call.call("sisnr_loss", mask.device, ctypes.byref(d), mixed, mask.detach(), target, phase, seq_len, ws, ws.numel(),
+                   loss, dmask, wav)
         ctx.dmask = dmask
         ctx.mark_non_differentiable(wav) if wav is not None else None
         return (loss, wav) if want_wav else loss
@@ -88,19 +68,16 @@ def sisnr_loss(mask, mixed, target, phase, seq_len, audio_cfg, return_wav: bool 
 class _PowerLaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mask, mixed, target, power, ratio):
-        lib = _lib.load()
         for n, t in (("mask", mask), ("mixed", mixed), ("target", target)):
-            _dev_check(t.detach(), n)
+            _call.dev_check(t.detach(), n)
         if mixed.shape != mask.shape or target.shape != mask.shape:
             raise ValueError(f"power_law_loss: shapes differ: mask {tuple(mask.shape)}, mixed {tuple(mixed.shape)}, "
                              f"target {tuple(target.shape)}")
         scratch = torch.empty(2, dtype=torch.float64, device=mask.device)
         loss = torch.empty((), dtype=torch.float32, device=mask.device)
         dmask = torch.empty_like(mask) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(mask.device):
-            rc = lib.vs_powerlaw_loss(_p(mixed), _p(mask.detach()), _p(target), mask.numel(), float(power), float(ratio),
-                                      _p(scratch), _p(loss), _p(dmask), _stream())
-        _lib.check(rc, "vs_powerlaw_loss")
+        _call.call("powerlaw_loss", mask.device, mixed, mask.detach(), target, mask.numel(), float(power), float(ratio),
+                   scratch, loss, dmask)
         ctx.dmask = dmask
         return loss
 

@@ -24,8 +24,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib
-from .ops import _p, _stream
+from . import _call, _lib
 
 TARGET_LUFS, PEAK_DB = -23.0, -2.0
 TRUE_PEAK_GROUP_BYTES = 256 << 20       # the 4x oversampled temporary of normalize(true_peak=True), per group of clips
@@ -86,14 +85,12 @@ class LoudnessMeter:
         ``table`` [N, 2] int64 on the host = (first sample in ``flat``, samples).  energy=True: a fifth value, the list of every
         clip's sub-block energies e_k (fp64 views of one device buffer)."""
         flat, table = _flat(flat, self.device), _table(table)
-        lib, N, dev = _lib.load(), table.shape[0], self.device
+        N, dev = table.shape[0], self.device
         if int(table[:, 1].min()) < 0:
             raise ValueError("table: a clip has a negative length")
         m = table[:, 1] // self.dims.sub
         laid_out = int(m.sum()) * self.dims.sub                       # sized as if the clips lay end to end (they may overlap)
-        nbytes = lib.vs_loudness_workspace_bytes(ctypes.byref(self.dims), max(laid_out, flat.numel()), N)
-        if nbytes == 0:
-            _lib.check(-1, "vs_loudness_workspace_bytes")
+        nbytes = _call.sized("loudness_workspace_bytes", ctypes.byref(self.dims), max(laid_out, flat.numel()), N)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         lufs = torch.empty(N, dtype=torch.float64, device=dev)
         peak = torch.empty(N, dtype=torch.float32, device=dev)
@@ -105,10 +102,8 @@ class LoudnessMeter:
             e = torch.empty(max(1, int(m.sum())), dtype=torch.float64, device=dev)
             e_at_dev = e_at.to(dev)
         table_dev = table.to(dev)
-        with torch.cuda.device(dev):
-            rc = lib.vs_loudness(ctypes.byref(self.dims), _p(flat), flat.numel(), _p(table), _p(table_dev), N, _p(lufs), _p(peak),
-                                 _p(counts), _p(valid), _p(e), _p(e_at_dev), _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "vs_loudness")
+        _call.call("loudness", dev, ctypes.byref(self.dims), flat, flat.numel(), table, table_dev, N, lufs, peak, counts, valid,
+                   e, e_at_dev, ws, ws.numel())
         if energy:
             return lufs, peak, counts, valid, [e[o:o + k] for o, k in zip(e_at.tolist(), m.tolist())]
         return lufs, peak, counts, valid
@@ -178,9 +173,7 @@ def scale_clips_(flat: torch.Tensor, table: torch.Tensor, gain: torch.Tensor) ->
     if gain.shape != (N,) or gain.dtype != torch.float32 or gain.device != dev or not gain.is_contiguous():
         raise ValueError(f"gain: expected a contiguous float32 [{N}] tensor on {dev}")
     table_dev = table.to(dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().vs_scale_clips(_p(flat), flat.numel(), _p(table), _p(table_dev), _p(gain), N, _stream())
-    _lib.check(rc, "vs_scale_clips")
+    _call.call("scale_clips", dev, flat, flat.numel(), table, table_dev, gain, N)
 
 
 def true_peaks(flat: torch.Tensor, table: torch.Tensor, sample_rate: int) -> torch.Tensor:
@@ -190,7 +183,7 @@ def true_peaks(flat: torch.Tensor, table: torch.Tensor, sample_rate: int) -> tor
     dev = _device(flat.device)
     flat, table = _flat(flat, dev), _table(table)
     rs = Resampler(int(sample_rate), 4 * int(sample_rate), dev)
-    lib, N = _lib.load(), table.shape[0]
+    N = table.shape[0]
     n_out = torch.tensor([rs.out_len(int(n)) for n in table[:, 1]], dtype=torch.int64)
     out = torch.empty(N, dtype=torch.float32, device=dev)
     lo = 0
@@ -206,9 +199,7 @@ def true_peaks(flat: torch.Tensor, table: torch.Tensor, sample_rate: int) -> tor
         rs.clips_into(flat, tmp, torch.cat((table[lo:hi], offsets[:-1, None]), dim=1))
         rng = torch.empty(hi - lo, 2, dtype=torch.float32, device=dev)
         offsets_dev = offsets.to(dev)
-        with torch.cuda.device(dev):
-            rc = lib.vs_clip_range(_p(tmp), tmp.numel(), _p(offsets), _p(offsets_dev), None, hi - lo, _p(rng), _stream())
-        _lib.check(rc, "vs_clip_range")
+        _call.call("clip_range", dev, tmp, tmp.numel(), offsets, offsets_dev, None, hi - lo, rng)
         out[lo:hi] = rng.abs().max(dim=1).values
         lo = hi
     return out

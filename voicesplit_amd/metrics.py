@@ -20,29 +20,7 @@ import ctypes
 
 import torch
 
-from . import _lib
-from .ops import _dev_check, _p, _stream
-
-_WS = {}
-
-
-def _buffer(n: int, device):
-    """The device's metric workspace, grown to n bytes: one buffer per device, shared by ``bss_sdr`` and ``bss_eval``."""
-    key = torch.device(device).index
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        _WS.pop(key, None)
-        ws = torch.empty(n, dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
-
-
-def _workspace(B: int, N: int, device):
-    lib = _lib.load()
-    n = lib.vs_sdr_workspace_bytes(B, N)
-    if n == 0:
-        _lib.check(-1, f"vs_sdr_workspace_bytes(B={B}, N={N})")
-    return _buffer(n, device)
+from . import _call, _lib
 
 
 def bss_sdr(reference: torch.Tensor, estimate: torch.Tensor):
@@ -67,27 +45,16 @@ def bss_sdr(reference: torch.Tensor, estimate: torch.Tensor):
     ref = reference.reshape(1, -1) if reference.dim() == 1 else reference
     est = estimate.reshape(1, -1) if estimate.dim() == 1 else estimate
     ref, est = ref.contiguous(), est.contiguous()
-    _dev_check(ref, "reference")
-    _dev_check(est, "estimate")
+    _call.dev_check(ref, "reference")
+    _call.dev_check(est, "estimate")
     if ref.device != est.device:
         raise ValueError(f"reference on {ref.device}, estimate on {est.device}")
     B, N = ref.shape
-    lib = _lib.load()
-    ws = _workspace(B, N, ref.device)
+    ws = _call.scratch("metric", _call.sized("sdr_workspace_bytes", B, N, what=f"vs_sdr_workspace_bytes(B={B}, N={N})"), ref.device)
     sdr = torch.empty(B, dtype=torch.float64, device=ref.device)
     status = torch.empty(B, dtype=torch.int32, device=ref.device)
-    with torch.cuda.device(ref.device):
-        rc = lib.vs_sdr(_p(ref), _p(est), B, N, _p(sdr), _p(status), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_sdr")
+    _call.call("sdr", ref.device, ref, est, B, N, sdr, status, ws, ws.numel())
     return sdr, status
-
-
-def _workspace_multi(B: int, K: int, N: int, device):
-    lib = _lib.load()
-    n = lib.vs_bss_eval_workspace_bytes(B, K, N)
-    if n == 0:
-        _lib.check(-1, f"vs_bss_eval_workspace_bytes(B={B}, K={K}, N={N})")
-    return _buffer(n, device)
 
 
 MAX_SOURCES = 6
@@ -124,21 +91,19 @@ def bss_eval(reference: torch.Tensor, estimate: torch.Tensor, compute_permutatio
     ref = reference.unsqueeze(0) if reference.dim() == 2 else reference
     est = estimate.unsqueeze(0) if estimate.dim() == 2 else estimate
     ref, est = ref.contiguous(), est.contiguous()
-    _dev_check(ref, "reference")
-    _dev_check(est, "estimate")
+    _call.dev_check(ref, "reference")
+    _call.dev_check(est, "estimate")
     if ref.device != est.device:
         raise ValueError(f"reference on {ref.device}, estimate on {est.device}")
     B, K, N = ref.shape
-    lib = _lib.load()
-    ws = _workspace_multi(B, K, N, ref.device)
+    ws = _call.scratch("metric", _call.sized("bss_eval_workspace_bytes", B, K, N,
+                                             what=f"vs_bss_eval_workspace_bytes(B={B}, K={K}, N={N})"), ref.device)
     sdr, sir, sar = (torch.empty(B, K, dtype=torch.float64, device=ref.device) for _ in range(3))
     perm = torch.empty(B, K, dtype=torch.int32, device=ref.device)
     status = torch.empty(B, dtype=torch.int32, device=ref.device)
     pairs = torch.empty(B, 3, K, K, dtype=torch.float64, device=ref.device) if return_pairs else None
-    with torch.cuda.device(ref.device):
-        rc = lib.vs_bss_eval(_p(ref), _p(est), B, K, N, 1 if compute_permutation else 0, _p(sdr), _p(sir), _p(sar), _p(perm),
-                             _p(status), _p(pairs), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_bss_eval")
+    _call.call("bss_eval", ref.device, ref, est, B, K, N, 1 if compute_permutation else 0, sdr, sir, sar, perm, status, pairs,
+               ws, ws.numel())
     return (sdr, sir, sar, perm, status, pairs) if return_pairs else (sdr, sir, sar, perm, status)
 
 
@@ -172,7 +137,7 @@ def stoi_clips(reference: torch.Tensor, estimate: torch.Tensor, table: torch.Ten
     kept frames Mk), int32 [R]; status 1 = fewer than 30 kept frames, d = 1e-5.  envelopes: two more values, the band envelopes as
     one flat float64 buffer and their offsets [R] int64 (host): pair i's X then Y as [2, 15, Mk_i] from its offset on."""
     for name, t in (("reference", reference), ("estimate", estimate)):
-        _dev_check(t, name)
+        _call.dev_check(t, name)
         if t.dim() != 1:
             raise ValueError(f"{name}: expected a flat 1-D buffer, got {tuple(t.shape)}")
     if reference.shape != estimate.shape or reference.device != estimate.device:
@@ -182,11 +147,9 @@ def stoi_clips(reference: torch.Tensor, estimate: torch.Tensor, table: torch.Ten
         raise ValueError("table: expected [R, 2] int64 on the host, R >= 1")
     table = table.contiguous()
     dev, R, total = reference.device, table.shape[0], reference.numel()
-    lib, dims = _lib.load(), stoi_plan()
-    need = lib.vs_stoi_workspace_bytes(ctypes.byref(dims), total, R)
-    if need == 0:
-        _lib.check(-1, f"vs_stoi_workspace_bytes(total={total}, R={R})")
-    ws = _buffer(need, dev)
+    dims = stoi_plan()
+    ws = _call.scratch("metric", _call.sized("stoi_workspace_bytes", ctypes.byref(dims), total, R,
+                                             what=f"vs_stoi_workspace_bytes(total={total}, R={R})"), dev)
     table_dev = table.to(dev)
     d = torch.empty(R, dtype=torch.float64, device=dev)
     frames = torch.empty(R, 2, dtype=torch.int32, device=dev)
@@ -197,10 +160,8 @@ def stoi_clips(reference: torch.Tensor, estimate: torch.Tensor, table: torch.Ten
         tob_at = counts.cumsum(0) - counts
         tob = torch.zeros(max(1, int(counts.sum())), dtype=torch.float64, device=dev)
         tob_at_dev = tob_at.to(dev)
-    with torch.cuda.device(dev):
-        rc = lib.vs_stoi(ctypes.byref(dims), _p(reference), _p(estimate), total, _p(table), _p(table_dev), R, 1 if extended else 0,
-                         _p(d), _p(frames), _p(status), _p(tob), _p(tob_at_dev), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_stoi")
+    _call.call("stoi", dev, ctypes.byref(dims), reference, estimate, total, table, table_dev, R, 1 if extended else 0,
+               d, frames, status, tob, tob_at_dev, ws, ws.numel())
     return (d, frames, status, tob, tob_at) if envelopes else (d, frames, status)
 
 
@@ -257,8 +218,8 @@ def _stoi_inputs(reference, estimate, sample_rate, lengths):
         n = n.repeat_interleave(rows // n.numel())
     ref = reference.reshape(-1, N).contiguous()
     est = estimate.reshape(-1, N).contiguous()
-    _dev_check(ref, "reference")
-    _dev_check(est, "estimate")
+    _call.dev_check(ref, "reference")
+    _call.dev_check(est, "estimate")
     if ref.device != est.device:
         raise ValueError(f"reference on {ref.device}, estimate on {est.device}")
     at = torch.arange(rows, dtype=torch.int64) * N

@@ -20,9 +20,8 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _call, _lib
 from .config import resolve_audio
-from .ops import _p, _stream
 
 MIN_CLIP = 1025                       # vs_trim_bounds: the reflect padding of 1024 samples needs y[1024]
 DEFAULT_FORMAT = {"emb": "*-emb.pt", "mixed": "*-mixed.pt", "target": "*-target.pt", "target_wav": "*-target.wav",
@@ -159,18 +158,11 @@ class ClipPool:
         self.peak = None
 
     def _trim(self):
-        lib = _lib.load()
         n = len(self)
-        nbytes = lib.vs_trim_workspace_bytes(self.total, n)
-        if nbytes == 0:
-            _lib.check(-1, "vs_trim_workspace_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = torch.empty(_call.sized("trim_workspace_bytes", self.total, n), dtype=torch.uint8, device=self.device)
         bounds = torch.empty(n, 2, dtype=torch.int32, device=self.device)
         peak = torch.empty(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = lib.vs_trim_bounds(_p(self.flat), self.total, _p(self.offsets), _p(self.offsets_dev), n, _p(bounds), _p(peak),
-                                    _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "vs_trim_bounds")
+        _call.call("trim_bounds", self.device, self.flat, self.total, self.offsets, self.offsets_dev, n, bounds, peak, ws, ws.numel())
         self.bounds, self.peak = bounds.cpu(), peak.cpu()
 
     def __len__(self) -> int:
@@ -184,13 +176,9 @@ class ClipPool:
             if self.flat is None:
                 raise _lib.VoiceSplitHipError("this pool holds no audio (ClipPool.planned without value_range=): the value ranges are "
                                               "computed on an MI355X (HIP) device only")
-            lib = _lib.load()
             out = torch.empty(len(self), 2, dtype=torch.float32, device=self.device)
             bounds = self.bounds.to(self.device)
-            with torch.cuda.device(self.device):
-                rc = lib.vs_clip_range(_p(self.flat), self.total, _p(self.offsets), _p(self.offsets_dev), _p(bounds), len(self),
-                                       _p(out), _stream())
-            _lib.check(rc, "vs_clip_range")
+            _call.call("clip_range", self.device, self.flat, self.total, self.offsets, self.offsets_dev, bounds, len(self), out)
             self._range = out.cpu()
         return self._range
 
@@ -322,7 +310,6 @@ def output_name(out_dir: str, pattern: str, num: int) -> str:
 def mix_clips(flat: torch.Tensor, clean_at: torch.Tensor, interf_at: torch.Tensor, L: int, invalid_count: Optional[torch.Tensor] = None):
     """vs_mix_clips: (mixed_wav [B, L], target_wav [B, L], norm [B], valid [B] int32) for the items starting at the absolute sample
     indices ``clean_at`` / ``interf_at`` ([B] int64 on the device) of ``flat``."""
-    lib = _lib.load()
     if not flat.is_cuda:
         raise _lib.VoiceSplitHipError(f"the pool is on {flat.device}: this path only runs on an MI355X (HIP) device; there is no CPU fallback")
     for name, t in (("clean_at", clean_at), ("interf_at", interf_at)):
@@ -336,10 +323,7 @@ def mix_clips(flat: torch.Tensor, clean_at: torch.Tensor, interf_at: torch.Tenso
     target = torch.empty(B, L, device=dev)
     norm = torch.empty(B, device=dev)
     valid = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.vs_mix_clips(_p(flat), flat.numel(), _p(clean_at), _p(interf_at), B, int(L), _p(mixed), _p(target), _p(norm), _p(valid),
-                              _p(invalid_count), _stream())
-    _lib.check(rc, "vs_mix_clips")
+    _call.call("mix_clips", dev, flat, flat.numel(), clean_at, interf_at, B, int(L), mixed, target, norm, valid, invalid_count)
     return mixed, target, norm, valid
 
 
@@ -609,7 +593,6 @@ def split_points(flat: torch.Tensor, regions: torch.Tensor, ratio: torch.Tensor,
     """vs_split_point: (count [B] int32, split [B] int32, intervals [B, cap, 2] int32 or None) on the device for the regions
     ``regions`` [B, 2] int64 = (at, n) of ``flat`` and ``ratio`` [B] float64 (host tensors; the library checks the regions on the
     host before it launches anything)."""
-    lib = _lib.load()
     if not flat.is_cuda:
         raise _lib.VoiceSplitHipError(f"the pool is on {flat.device}: this path only runs on an MI355X (HIP) device; there is no CPU fallback")
     regions = regions.to(torch.int64).cpu().contiguous()
@@ -618,18 +601,13 @@ def split_points(flat: torch.Tensor, regions: torch.Tensor, ratio: torch.Tensor,
     if regions.shape != (B, 2) or ratio.shape != (B,) or B == 0:
         raise ValueError("split_points: regions [B, 2] and ratio [B], B > 0")
     dev = flat.device
-    nbytes = lib.vs_split_workspace_bytes(max(int(regions[:, 1].max()), 0), B)
-    if nbytes == 0:
-        _lib.check(-1, "vs_split_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(_call.sized("split_workspace_bytes", max(int(regions[:, 1].max()), 0), B), dtype=torch.uint8, device=dev)
     count = torch.empty(B, dtype=torch.int32, device=dev)
     split = torch.empty(B, dtype=torch.int32, device=dev)
     intervals = torch.full((B, cap, 2), -1, dtype=torch.int32, device=dev) if cap > 0 else None
     regions_dev, ratio_dev = regions.to(dev), ratio.to(dev)
-    with torch.cuda.device(dev):
-        rc = lib.vs_split_point(_p(flat), flat.numel(), _p(regions), _p(regions_dev), _p(ratio_dev), B, _p(count), _p(split),
-                                _p(intervals), int(cap), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_split_point")
+    _call.call("split_point", dev, flat, flat.numel(), regions, regions_dev, ratio_dev, B, count, split, intervals, int(cap),
+               ws, ws.numel())
     return count, split, intervals
 
 
@@ -637,7 +615,6 @@ def mix_sequence(flat: torch.Tensor, noise: torch.Tensor, items: torch.Tensor, L
                  rows: bool = True, invalid_count: Optional[torch.Tensor] = None):
     """vs_mix_sequence: (mixed_wav [B, L], target_wav [B, L], norm [B], aux [B, 8], valid [B] int32) for the ``vs_seq_item`` rows
     ``items`` [B, 136] uint8 on the device.  rows=False: the maximum only (mixed_wav and target_wav are None)."""
-    lib = _lib.load()
     if not flat.is_cuda:
         raise _lib.VoiceSplitHipError(f"the pool is on {flat.device}: this path only runs on an MI355X (HIP) device; there is no CPU fallback")
     dev = flat.device
@@ -653,10 +630,8 @@ def mix_sequence(flat: torch.Tensor, noise: torch.Tensor, items: torch.Tensor, L
     norm = torch.empty(B, device=dev)
     aux = torch.empty(B, 8, device=dev)
     valid = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.vs_mix_sequence(_p(flat), flat.numel(), _p(noise), noise.numel(), _p(items), B, int(L), int(R), _p(norm_in), _p(mixed),
-                                 _p(target), _p(norm), _p(aux), _p(valid), _p(invalid_count), _stream())
-    _lib.check(rc, "vs_mix_sequence")
+    _call.call("mix_sequence", dev, flat, flat.numel(), noise, noise.numel(), items, B, int(L), int(R), norm_in, mixed, target, norm,
+               aux, valid, invalid_count)
     return mixed, target, norm, aux, valid
 
 

@@ -13,8 +13,7 @@ from typing import Callable, List, Optional, Sequence
 
 import torch
 
-from . import _lib
-from .ops import _p, _stream
+from . import _call, _lib
 
 
 def plan(sr_in: int, sr_out: int) -> _lib.VsResampleDims:
@@ -59,9 +58,7 @@ class Resampler:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.bank = torch.empty(self.dims.L * self.dims.T, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = _lib.load().vs_resample_bank(ctypes.byref(self.dims), _p(self.bank), _stream())
-        _lib.check(rc, "vs_resample_bank")
+        _call.call("resample_bank", self.device, ctypes.byref(self.dims), self.bank)
 
     def out_len(self, n_in: int) -> int:
         return out_len(self.dims, n_in)
@@ -86,10 +83,8 @@ class Resampler:
         out = self._rows(out, "out")
         if out.shape != (B, int(y_count)):
             raise ValueError(f"out: expected [{B}, {y_count}], got {tuple(out.shape)}")
-        with torch.cuda.device(self.device):
-            rc = _lib.load().vs_resample(ctypes.byref(self.dims), _p(self.bank), _p(buf), int(x_first), buf.shape[1], buf.stride(0),
-                                         int(stream_len), _p(out), int(y_first), int(y_count), out.stride(0), B, _stream())
-        _lib.check(rc, "vs_resample")
+        _call.call("resample", self.device, ctypes.byref(self.dims), self.bank, buf, int(x_first), buf.shape[1], buf.stride(0),
+                   int(stream_len), out, int(y_first), int(y_count), out.stride(0), B)
         return out
 
     def __call__(self, wav: torch.Tensor) -> torch.Tensor:
@@ -109,10 +104,8 @@ class Resampler:
             raise ValueError("table: expected [N, 3] int64 on the host")
         table = table.contiguous()
         table_dev = table.to(self.device)
-        with torch.cuda.device(self.device):
-            rc = _lib.load().vs_resample_clips(ctypes.byref(self.dims), _p(self.bank), _p(flat_in), flat_in.numel(), _p(out), out.numel(),
-                                               _p(table), _p(table_dev), table.shape[0], _stream())
-        _lib.check(rc, "vs_resample_clips")
+        _call.call("resample_clips", self.device, ctypes.byref(self.dims), self.bank, flat_in, flat_in.numel(), out, out.numel(),
+                   table, table_dev, table.shape[0])
 
     def clips(self, wavs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
         """1-D waveforms of unequal length (host or device) -> their resampled versions, views into one flat device buffer, from

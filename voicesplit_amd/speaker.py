@@ -21,23 +21,12 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _call, _lib
 from .config import resolve_audio
 from .losses import loss_dims
-from .ops import MATH_CODES, _dev_check, _p, _stream
+from .ops import MATH_CODES
 
-_WS = {}
 _BASIS = {}
-
-
-def _workspace(nbytes: int, device, slot: str):
-    key = (slot, torch.device(device).index)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _WS.pop(key, None)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
 
 
 # ---- mel filterbank: librosa.filters.mel(sr, n_fft, n_mels) with its defaults, restated in fp64 ---------------------------
@@ -92,23 +81,17 @@ def _basis_on(device, sr: int, n_fft: int, n_mels: int) -> torch.Tensor:
 
 def logmel(wav: torch.Tensor, audio_cfg, num_mels: int = 40) -> torch.Tensor:
     """ap.get_mel on the device: wav [n] (any n > n_fft / 2) -> [num_mels, 1 + n // hop_length] log10 mel power."""
-    lib = _lib.load()
-    _dev_check(wav, "wav")
+    _call.dev_check(wav, "wav")
     if wav.dim() != 1:
         raise ValueError(f"wav: expected one clip [n], got {tuple(wav.shape)}")
     n = wav.numel()
     audio_cfg = resolve_audio(audio_cfg)
     n_fft, hop = int(audio_cfg["n_fft"]), int(audio_cfg["hop_length"])
     d = loss_dims(1, 1 + n // hop, n_fft // 2 + 1, audio_cfg)
-    nbytes = lib.vs_logmel_workspace_bytes(ctypes.byref(d), n, int(num_mels))
-    if nbytes == 0:
-        _lib.check(-1, "vs_logmel_workspace_bytes")
-    ws = _workspace(nbytes, wav.device, "logmel")
+    ws = _call.scratch("logmel", _call.sized("logmel_workspace_bytes", ctypes.byref(d), n, int(num_mels)), wav.device)
     basis = _basis_on(wav.device, int(audio_cfg.get("sample_rate", 16000)), n_fft, int(num_mels))
     mel = torch.empty(int(num_mels), 1 + n // hop, device=wav.device)
-    with torch.cuda.device(wav.device):
-        rc = lib.vs_wav_to_logmel(ctypes.byref(d), _p(wav), n, _p(basis), int(num_mels), _p(mel), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "vs_wav_to_logmel")
+    _call.call("wav_to_logmel", wav.device, ctypes.byref(d), wav, n, basis, int(num_mels), mel, ws, ws.numel())
     return mel
 
 
@@ -174,10 +157,9 @@ class SpeakerEncoder(nn.Module):
 
     def _prepare(self, device):
         """The packed weights, rebuilt when a parameter was replaced, edited in place (version counter) or the arithmetic changed."""
-        lib = _lib.load()
         ps = self._param_list()
         for p in ps:
-            _dev_check(p.detach(), "SpeakerEncoder parameter")
+            _call.dev_check(p.detach(), "SpeakerEncoder parameter")
             if p.device != device:
                 raise ValueError(f"SpeakerEncoder parameters are on {p.device}, the input on {device}")
         key = (self.math,) + tuple((p.data_ptr(), p._version) for p in ps)
@@ -185,17 +167,12 @@ class SpeakerEncoder(nn.Module):
         if prep is not None and prep[0] == key:
             return prep[1]
         d = self._dims()
-        nbytes = lib.vs_speaker_prepared_bytes(ctypes.byref(d))
-        if nbytes == 0:
-            _lib.check(-1, "vs_speaker_prepared_bytes")
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        buf = torch.empty(_call.sized("speaker_prepared_bytes", ctypes.byref(d)), dtype=torch.uint8, device=device)
         sp = _lib.VsSpeakerParams()
         for k in range(self.lstm_layers):
             sp.w_ih[k], sp.w_hh[k], sp.b_ih[k], sp.b_hh[k] = (p.data_ptr() for p in ps[4 * k:4 * k + 4])
         sp.proj_w, sp.proj_b = ps[-2].data_ptr(), ps[-1].data_ptr()
-        with torch.cuda.device(device):
-            rc = lib.vs_speaker_prepare(ctypes.byref(d), ctypes.byref(sp), _p(buf), buf.numel(), _stream())
-        _lib.check(rc, "vs_speaker_prepare")
+        _call.call("speaker_prepare", device, ctypes.byref(d), ctypes.byref(sp), buf, buf.numel())
         self.__dict__["_prepared"] = (key, buf)
         return buf
 
@@ -204,11 +181,10 @@ class SpeakerEncoder(nn.Module):
         """All windows of all utterances as ONE batch.  mels: list of [num_mels, T_u] device tensors.
         Returns (dvec [U, emb_dim], valid [U] bool): a clip shorter than one window has valid = False and a zero row.
         return_stages: also h_last [N, lstm_hidden], proj [N, emb_dim] (un-normalised) and the window offsets [U + 1]."""
-        lib = _lib.load()
         if len(mels) == 0:
             raise ValueError("embed_many: empty list")
         for m in mels:
-            _dev_check(m, "mel")
+            _call.dev_check(m, "mel")
             if m.dim() != 2 or m.shape[0] != self.num_mels:
                 raise ValueError(f"mel: expected [{self.num_mels}, T], got {tuple(m.shape)}")
         device = mels[0].device
@@ -222,22 +198,17 @@ class SpeakerEncoder(nn.Module):
         prepared = self._prepare(device)
         mel = (mels[0] if U == 1 else torch.cat(list(mels), dim=1)).detach().contiguous()
         d = self._dims()
-        nbytes = lib.vs_speaker_workspace_bytes(ctypes.byref(d), N, total)
-        if nbytes == 0:
-            _lib.check(-1, "vs_speaker_workspace_bytes")
-        ws = _workspace(nbytes, device, "embed")
+        ws = _call.scratch("embed", _call.sized("speaker_workspace_bytes", ctypes.byref(d), N, total), device)
         offs = torch.tensor([frames, wins], dtype=torch.int32).to(device)
         h_last = torch.empty(N, self.lstm_hidden, device=device) if return_stages else None
         proj = torch.empty(N, self.emb_dim, device=device) if return_stages else None
-        with torch.cuda.device(device):
-            rc = lib.vs_speaker_embed(ctypes.byref(d), _p(prepared), prepared.numel(), _p(mel), total, _p(offs[0]), _p(offs[1]), U, N,
-                                      _p(h_last), _p(proj), _p(dvec), _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "vs_speaker_embed")
+        _call.call("speaker_embed", device, ctypes.byref(d), prepared, prepared.numel(), mel, total, offs[0], offs[1], U, N,
+                   h_last, proj, dvec, ws, ws.numel())
         return (dvec, valid) + ((h_last, proj, wins) if return_stages else ())
 
     def forward(self, mel: torch.Tensor) -> torch.Tensor:
         """mel [num_mels, T] -> d-vector [emb_dim] (the notebook's forward)."""
-        _dev_check(mel, "mel")
+        _call.dev_check(mel, "mel")
         if mel.dim() != 2 or mel.shape[0] != self.num_mels:
             raise ValueError(f"mel: expected [{self.num_mels}, T], got {tuple(mel.shape)}")
         if mel.shape[1] < self.window:
