@@ -1170,6 +1170,64 @@ int vs_stoi(const vs_stoi_dims* dims, const float* ref, const float* est, long l
             const long long* clips, int R, int extended, double* d, int* frames, int* status, double* tob, const long long* tob_at,
             void* workspace, size_t workspace_bytes, void* stream);
 
+/* =============================================================================================
+ * ABI 11 (additive entries).  Reverberation: room impulse responses of a shoebox room by the image method, a per-row FIR that applies
+ * them, and the energy of a row (the level control of the reverberant mixtures).  The image method is RESTATED (Allen & Berkley 1979),
+ * NOT COMPARED WITH A PYROOMACOUSTICS OR RIR-GENERATOR RUN: neither package was available where this was written.  This text is the
+ * contract; tests/reverb_ref.py restates it in fp64.
+ *
+ * vs_room: one response.  size = (L_x, L_y, L_z) in metres, src = s and mic = m inside the room (0 < s < L, 0 < m < L per axis),
+ * beta = reflection coefficients of the walls (x0, x1, y0, y1, z0, z1), each in -1 .. 1, c in m/s, fs in Hz, 1 <= nh <= 8192 taps,
+ * max_order >= 0 or -1 = no limit.
+ * Image sum: for parities q, j, k in {0, 1} and integers n, l, p
+ *   R   = ((1 - 2q) s_x - m_x + 2 n L_x, (1 - 2j) s_y - m_y + 2 l L_y, (1 - 2k) s_z - m_z + 2 p L_z)
+ *   d   = sqrt((R_x^2 + R_y^2) + R_z^2),  tau = d fs / c
+ *   amp = beta_x0^|n - q| beta_x1^|n| beta_y0^|l - j| beta_y1^|l| beta_z0^|p - k| beta_z1^|p| / (4 pi d),  0^0 = 1
+ * an image is dropped when max_order >= 0 and |2n - q| + |2l - j| + |2p - k| > max_order.
+ *   h[t] = sum amp w(t - tau), t = 0 .. nh - 1;  w(u) = sinc(u) (1 + cos(pi u / 40)) / 2 for |u| < 40, else 0, sinc(u) = sin(pi u) / (pi u)
+ * An image with tau - 40 >= nh adds nothing: |n| <= floor((nh + 40) c / (2 fs L_x)) + 1 covers every other one (likewise l, p).
+ * Everything is fp64 and h[t] is rounded ONCE to fp32.  u is formed as (t - rint(tau)) - (tau - rint(tau)) and sin(pi u) as
+ * -(-1)^(t - rint(tau)) sinpi(tau - rint(tau)): one sine per image.  Every tap adds its images in ONE order, the enumeration order of
+ * (q, j, k, n, l, p) with p running fastest (an image whose window misses the tap adds exactly 0 and may be skipped), so the bits of a
+ * response depend on its descriptor alone: not on its row, its neighbours, R or the call.  No atomics.
+ * rooms_host [R] in HOST memory is checked before anything is launched; rooms [R] is the same table on the device.  Refused with -1
+ * and a message: a non-positive size, a source or receiver outside the room, d = 0 (source on the receiver), beta outside -1 .. 1,
+ * non-positive c or fs, nh outside 1 .. min(8192, H), max_order < -1, a room so small that the response has more than 2^24 images.
+ * h [R][H] fp32 on the device, 1 <= H <= 8192: row r holds its nh taps, then zeros.  1 <= R <= 65535.  A memset and one launch.
+ *
+ * vs_fir_rows: y[b][i] = sum_{k < nh[b]} h[hrow[b]][k] x(at[b] + i - k), i = 0 .. L - 1, where x(p) = samples[p] of the flat buffer for
+ * lo[b] <= p, and 0 below lo[b].  at, lo [B] int64 and nh, hrow [B] int32 on the device; h [R][H] fp32; y [B][L].  Any alignment of
+ * at.  Nothing outside [lo[b], at[b] + L) is read.  A row with lo < 0, lo > at, at + L > total, hrow outside 0 .. R - 1 or nh outside
+ * 1 .. H is not read: valid[b] = -1 and a row of zeros; otherwise valid[b] = 1.  Host-checkable argument errors (NULL, B outside
+ * 1 .. 65535, L outside 1 .. 2^24, H outside 1 .. 8192, total < L, an unknown math) return -1 and a message.
+ *   VS_MATH_FP32:  acc = 0; for k = 0 .. nh - 1 ascending: acc = fmaf(h[k], x(at + i - k), acc).  h = {1.0f} returns x bit for bit.
+ *   VS_MATH_F16X3: with mx = max |x| over the samples the row reads ([max(lo, at - nh + 1), at + L)) and mh = max |h[0 .. nh)|,
+ *     sx = 2^ex with 2^14 <= mx sx < 2^15 and sh likewise (exponents clamped to +-100; 1 for a maximum of 0); every x sx and h sh is
+ *     split into f16 hi = f16(v), lo = f16(v - hi); y = (sum hi_x hi_h + sum (hi_x lo_h + lo_x hi_h)) / (sx sh), the products on
+ *     v_mfma_f32_32x32x16_f16 with fp32 accumulation (lo lo is dropped).  K = nh + 32 is walked in one order that depends on neither
+ *     B, the row index nor the tile, from zero accumulators.  The bits of a row depend on its own samples (those it reads) and its
+ *     own filter alone; not on at mod 8, its position in the batch, B or the call.  Samples in [lo, at - nh + 1) belong to no product
+ *     of the row: they do not enter mx and are not multiplied (whatever their size, they cannot overflow an f16 plane).
+ *     Error against the exact sum, per output: <= (2^-20 + (nh + 32) 2^-23) sum_k |h_k| |x_{n-k}| + u, where u covers the lo planes
+ *     that fall into the f16 subnormals (spacing 2^-24: an error of 2^-25 / s per element):  u = nh 2^-38 mx mh
+ *     (2^-25 / sx <= 2^-39 mx per sample, times |h| <= mh, plus the same for the taps), for mx, mh above 2^-85.
+ * scale [B][4] fp32 (output; also this call's scratch): sx, 1 / sx, sh, 1 / sh of the row (1 for an invalid row); computed in both
+ * arithmetics, used by VS_MATH_F16X3 alone.  Two launches.
+ *
+ * vs_row_energy: energy[b] = sum_i double(y[b][i])^2 in fp64, y [B][L]: one workgroup per row, thread t adds samples t, t + 256, ..
+ * in ascending order, then a fixed binary fold of the 256 partial sums.  No atomics: two calls give the same bits.
+ * ============================================================================================= */
+typedef struct vs_room {
+  double size[3], src[3], mic[3];
+  double beta[6];                        /* x0, x1, y0, y1, z0, z1 */
+  double c, fs;
+  int nh, max_order;
+} vs_room;
+int vs_rir_shoebox(const vs_room* rooms_host, const vs_room* rooms, int R, int H, float* h, void* stream);
+int vs_fir_rows(const float* samples, long long total, const long long* at, const long long* lo, const int* nh, const int* hrow, int B,
+                int L, const float* h, int R, int H, int math, float* y, int* valid, float* scale, void* stream);
+int vs_row_energy(const float* y, int B, int L, double* energy, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -84,6 +84,11 @@ class VsStoiDims(Structure):
                                                                                  ("clip", c_double), ("dyn_db", c_double)]
 
 
+class VsRoom(Structure):
+    _fields_ = [("size", c_double * 3), ("src", c_double * 3), ("mic", c_double * 3), ("beta", c_double * 6), ("c", c_double),
+                ("fs", c_double), ("nh", c_int), ("max_order", c_int)]
+
+
 class VsConvLayerGrad(Structure):
     _fields_ = [(n, c_void_p) for n in ("weight", "bias", "bn_weight", "bn_bias")]
 
@@ -282,6 +287,10 @@ SIGNATURES = {
     "vs_stoi_plan": (c_int, [POINTER(VsStoiDims)]),
     "vs_stoi_workspace_bytes": (c_size_t, [POINTER(VsStoiDims), c_longlong, c_int]),
     "vs_stoi": (c_int, [POINTER(VsStoiDims), _P, _P, c_longlong, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    # reverberation: image-method room responses, the per-row FIR, row energies
+    "vs_rir_shoebox": (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    "vs_fir_rows": (c_int, [_P, c_longlong, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "vs_row_energy": (c_int, [_P, c_int, c_int, _P, _P]),
 }
 
 _lib = None

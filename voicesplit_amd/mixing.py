@@ -339,12 +339,35 @@ class MixtureBatches:
     Per epoch the host plans every batch's indices and copies them to the device once; per batch it enqueues vs_mix_clips, the two
     front-end calls and the embedding gather -- no ``.item()``, no blocking copy.  ``target_wav`` stays on the device.
     Items that vs_mix_clips marks invalid (a crop whose sum is all zero: rows of zeros) are counted on the device; the count is
-    read once behind every epoch (``invalid_items``) and reported as a warning."""
+    read once behind every epoch (``invalid_items``) and reported as a warning.
+
+    rir_pool (a ``reverb.RirPool``) and / or sir_db = (low, high): the two talkers in a room and / or at a drawn target-to-interferer
+    ratio (``_reverberant``); with both None, the default, the path above is the one that runs.  history: "clip" = the reverberation
+    of what the clip holds in front of the crop (from its trimmed start) rings into the crop, "zero" = silence in front of the crop.
+    target: "reverberant" = the clean talker with the full response, "early" = with the response cut 50 ms behind the direct path
+    (the mixture keeps the full response).  math: the FIR's arithmetic, "f16x3" (matrix cores) or "fp32".
+    A drawn pool belongs to ONE epoch: when ``items`` / ``epoch`` is asked for another epoch than ``rir_pool.epoch``, ``self.rir_pool``
+    is replaced by ``rir_pool.redraw(epoch)`` (the object that was passed in is left as it is) -- a host loop over the rooms and one
+    ``vs_rir_shoebox`` call, tens of milliseconds for a few hundred responses, once per epoch.  This holds for epoch 0 too: a pool
+    built with ``epoch=3`` and used for epoch 0 (``write_dataset``) is redrawn.  ``RirPool.from_rooms`` pools are fixed and never redrawn."""
 
     def __init__(self, pool: ClipPool, triplets: Sequence[Triplet], emb_table: torch.Tensor, audio_cfg, audio_len, shard,
-                 crop: str = "head", seed: int = 0, emb_rows: str = "clip"):
+                 crop: str = "head", seed: int = 0, emb_rows: str = "clip", rir_pool=None, sir_db=None, history: str = "clip",
+                 target: str = "reverberant", math: str = "f16x3"):
         if crop not in ("head", "random"):
             raise ValueError(f"crop must be 'head' or 'random', got {crop!r}")
+        if history not in ("clip", "zero"):
+            raise ValueError(f"history must be 'clip' or 'zero', got {history!r}")
+        if target not in ("reverberant", "early"):
+            raise ValueError(f"target must be 'reverberant' or 'early', got {target!r}")
+        if math not in ("f16x3", "fp32"):
+            raise ValueError(f"math must be 'f16x3' or 'fp32', got {math!r}")
+        if sir_db is not None:
+            sir_db = (float(sir_db[0]), float(sir_db[1]))
+            if not sir_db[0] <= sir_db[1]:
+                raise ValueError(f"sir_db must be (low, high) in dB with low <= high, got {sir_db}")
+        self.rir_pool, self.sir_db, self.history, self.target, self.math = rir_pool, sir_db, history, target, math
+        self._gain_tables = {}
         if emb_rows not in ("clip", "triplet"):
             raise ValueError(f"emb_rows must be 'clip' or 'triplet', got {emb_rows!r}")
         self.pool, self.acfg, self.shard, self.crop, self.seed = pool, audio_cfg, shard, crop, int(seed)
@@ -396,17 +419,76 @@ class MixtureBatches:
         pos, at, emb_row = self.plan(index_batches, epoch)
         at_dev, row_dev = at.to(self.device), emb_row.to(self.device)              # once per epoch
         lo = 0
+        reverberant = self.rir_pool is not None or self.sir_db is not None
+        if reverberant:
+            draws = self._reverb_plan(pos, epoch)
         for b in index_batches:
             hi = lo + len(b)
-            mixed_wav, target_wav, norm, valid = mix_clips(self.pool.flat, at_dev[0, lo:hi], at_dev[1, lo:hi], self.L, self._invalid)
+            if reverberant:
+                mixed_wav, target_wav, norm, valid, rows = self._reverberant(at_dev[:, lo:hi], {k: v[..., lo:hi] for k, v in draws.items()})
+            else:
+                mixed_wav, target_wav, norm, valid = mix_clips(self.pool.flat, at_dev[0, lo:hi], at_dev[1, lo:hi], self.L, self._invalid)
             mixed, phase = audio.wav_to_spec(mixed_wav, self.acfg, want_phase=True)
             target, _ = audio.wav_to_spec(target_wav, self.acfg, want_phase=False)
             emb = self.emb_table.index_select(0, row_dev[lo:hi])
             seq_len = torch.full((len(b),), self.L, dtype=torch.int64, device=self.device)
-            yield {"emb": emb, "target": target, "mixed": mixed, "seq_len": seq_len, "target_wav": target_wav, "phase": phase,
-                   "mixed_wav": mixed_wav, "norm": norm, "valid": valid, "positions": pos[lo:hi]}
+            item = {"emb": emb, "target": target, "mixed": mixed, "seq_len": seq_len, "target_wav": target_wav, "phase": phase,
+                    "mixed_wav": mixed_wav, "norm": norm, "valid": valid, "positions": pos[lo:hi]}
+            if reverberant:
+                item["rows"] = rows                                                # [2 B, L]: the clean and the scaled interferer rows
+            yield item
             lo = hi
         self._report_invalid()
+
+    # -- the two talkers in a room, at a drawn level ----------------------------------------------------------------------------------
+    def _reverb_plan(self, pos: torch.Tensor, epoch: int) -> dict:
+        """One epoch's per-item draws (a generator of their own: the crops are those of the epoch without reverberation) and row
+        tables, on the device: hrow / nh / nh_early [2, n] (clean, interferer), lo [2, n] and sir [n]."""
+        from . import reverb
+        if self.rir_pool is None:
+            self.rir_pool = reverb.RirPool.impulses(self.device)
+        elif self.rir_pool.epoch != epoch:
+            self.rir_pool = self.rir_pool.redraw(epoch)                            # fresh rooms every epoch (a fixed pool returns itself)
+        pool = self.rir_pool
+        rank = self.shard.rank if self.shard is not None else 0
+        room, sir = reverb.item_draws(self.seed, epoch, rank, pos.numel(), len(pool), self.sir_db)
+        hrow = torch.stack((2 * room, 2 * room + 1))
+        d = {"hrow": hrow.to(torch.int32), "nh": pool.nh_host[hrow], "nh_early": pool.nh_early_host[hrow], "sir": sir[None]}
+        if self.history == "clip":
+            d["lo"] = self.start[pos].t().contiguous()
+        return {k: v.contiguous().to(self.device) for k, v in d.items()}
+
+    def _reverberant(self, at: torch.Tensor, d: dict):
+        """One batch: vs_fir_rows writes the clean rows, the interferer rows (and for target="early" the clean rows once more, with
+        the cut response) into a scratch [2 B (+ B), L]; vs_row_energy; the interferer rows times g = sqrt(E_c / E_i 10^(-sir / 10));
+        then the unchanged vs_mix_clips on the scratch.  Returns its four tensors and the 2 B rows it mixed."""
+        from . import reverb
+        B, L, pool, dev = at.shape[1], self.L, self.rir_pool, self.device
+        early = self.target == "early"
+        rows = 3 * B if early else 2 * B
+        at2 = at.reshape(-1)
+        lo2 = d["lo"].reshape(-1) if "lo" in d else at2
+        hrow, nh = d["hrow"].reshape(-1), d["nh"].reshape(-1)
+        if early:
+            at2, lo2 = torch.cat((at2, at2[:B])), torch.cat((lo2, lo2[:B]))
+            hrow, nh = torch.cat((hrow, hrow[:B])), torch.cat((nh, d["nh_early"][0]))
+        scratch, _, _ = reverb.fir_rows(self.pool.flat, at2.contiguous(), lo2.contiguous(), nh.contiguous(), hrow.contiguous(), pool.h, L,
+                                        self.math)
+        if self.sir_db is not None:
+            e = reverb.row_energy(scratch[:2 * B])
+            ratio = e[:B] / e[B:] * torch.pow(10.0, -d["sir"][0] / 10.0)
+            g = torch.where(e[B:] > 0, ratio.sqrt(), torch.ones_like(ratio)).to(torch.float32)
+            if B not in self._gain_tables:                                         # the interferer rows of the scratch as a clip table
+                table = torch.stack((torch.arange(B, 2 * B, dtype=torch.int64) * L, torch.full((B,), L, dtype=torch.int64)), dim=1)
+                self._gain_tables[B] = (table.contiguous(), table.to(dev))
+            table, table_dev = self._gain_tables[B]
+            _call.call("scale_clips", dev, scratch, scratch.numel(), table, table_dev, g, B)
+        row_at = torch.arange(2 * B, dtype=torch.int64, device=dev) * L
+        mixed_wav, target_wav, norm, valid = mix_clips(scratch.reshape(-1), row_at[:B], row_at[B:], L, self._invalid)
+        if early:
+            ok = (valid == 1)[:, None]
+            target_wav = torch.where(ok, scratch[2 * B:] / norm[:, None], torch.zeros_like(target_wav))
+        return mixed_wav, target_wav, norm, valid, scratch[:2 * B]
 
     def _report_invalid(self):
         n = int(self._invalid.item())                                              # once per epoch
@@ -787,10 +869,11 @@ class OverlayBatches:
 # the reference's on-disk dataset (preprocess_by_csv.py)
 # ---------------------------------------------------------------------------------------------
 def write_dataset(pool: ClipPool, triplets: Sequence[Triplet], numbers: Sequence[int], out_dir: str, audio_cfg, audio_len,
-                  form=None, batch: int = 64, encoder=None) -> int:
+                  form=None, batch: int = 64, encoder=None, reverb: Optional[dict] = None) -> int:
     """What mix_wavfiles leaves in ``out_dir`` for every kept triplet, named by its CSV row number: ``*-mixed.wav``, ``*-target.wav``,
     ``*-emb.wav`` (float32 wavs), ``*-mixed.pt``, ``*-target.pt`` ([T, F] spectrograms), and with ``encoder`` ``*-emb.pt``.  Triplets
-    with a too short clean or interferer clip leave no files, as in the reference.  Returns the number of triplets written."""
+    with a too short clean or interferer clip leave no files, as in the reference.  Returns the number of triplets written.
+    reverb: None, or the ``rir_pool`` / ``sir_db`` / ``history`` / ``target`` / ``seed`` arguments of ``MixtureBatches`` (epoch 0)."""
     import numpy as np
     from scipy.io import wavfile
     form = dict(DEFAULT_FORMAT, **(form or {}))
@@ -809,7 +892,7 @@ def write_dataset(pool: ClipPool, triplets: Sequence[Triplet], numbers: Sequence
         has_emb = (table.abs().sum(dim=1) > 0).tolist()
         table = table.cpu()
     emb_table = torch.zeros(len(pool), 1, device=pool.device)                      # the writer does not use the yielded embedding
-    mb = MixtureBatches(pool, kept, emb_table, audio_cfg, audio_len, None, crop="head")
+    mb = MixtureBatches(pool, kept, emb_table, audio_cfg, audio_len, None, crop="head", **(reverb or {}))
     batches = [list(range(lo, min(lo + batch, len(kept)))) for lo in range(0, len(kept), batch)]
     for it in mb.items(batches):
         host = {k: it[k].cpu() for k in ("mixed_wav", "target_wav", "mixed", "target")}
@@ -891,6 +974,27 @@ def write_overlay_dataset(pool: ClipPool, noise_pool: ClipPool, triplets: Sequen
     return len(written), dict(ob.dropped)
 
 
+def add_reverb_arguments(ap) -> None:
+    ap.add_argument("--reverb-rooms", type=int, default=0, metavar="R", help="put the two talkers of every mixture in one of R random "
+                    "shoebox rooms (image-method responses made on the device, two sources and one receiver per room)")
+    ap.add_argument("--rt60", type=float, nargs=2, default=(0.15, 0.5), metavar=("LO", "HI"), help="--reverb-rooms: the rooms' "
+                    "reverberation times in seconds, uniform in LO .. HI")
+    ap.add_argument("--sir-db", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="scale the interferer so that the "
+                    "target-to-interferer energy ratio of every mixture is uniform in LO .. HI dB")
+
+
+def reverb_arguments(args, sample_rate: int, device, seed: int) -> Optional[dict]:
+    """The ``MixtureBatches`` arguments of --reverb-rooms / --rt60 / --sir-db; None without them (the path that runs is then the
+    one without reverberation, line for line)."""
+    if not args.reverb_rooms and args.sir_db is None:
+        return None
+    out = {"sir_db": None if args.sir_db is None else tuple(args.sir_db), "seed": seed}
+    if args.reverb_rooms:
+        from .reverb import RirPool
+        out["rir_pool"] = RirPool(args.reverb_rooms, device, seed=seed, rt60=tuple(args.rt60), fs=sample_rate)
+    return out
+
+
 def main(argv=None):
     from .config import load_config
     ap = argparse.ArgumentParser(description="Write the training / test triplet datasets of preprocess_by_csv.py, mixed on the GPU")
@@ -911,10 +1015,13 @@ def main(argv=None):
     ap.add_argument("--no-overlay", action="store_true", help="preprocess_by_csv_without_voice_overlay.py: the speakers take turns "
                     "over two noise recordings, four items (%%06d_1 .. _4) per triplet; needs --noise-csv")
     ap.add_argument("--noise-csv", default=None, help="--no-overlay: one noise file per line, relative to the dataset root")
-    ap.add_argument("--seed", type=int, default=0, help="--no-overlay: seed of the draws")
+    ap.add_argument("--seed", type=int, default=0, help="--no-overlay, --reverb-rooms, --sir-db: seed of the draws")
+    add_reverb_arguments(ap)
     args = ap.parse_args(argv)
     if args.no_overlay != bool(args.noise_csv):
         ap.error("--no-overlay and --noise-csv go together")
+    if args.no_overlay and (args.reverb_rooms or args.sir_db):
+        ap.error("--reverb-rooms and --sir-db serve the overlaid mixtures only, not --no-overlay")
     c = load_config(args.config)
     audio_cfg = resolve_audio(c.audio)
     form = c.dataset["format"] if "dataset" in c and "format" in c.dataset else None
@@ -942,7 +1049,8 @@ def main(argv=None):
             continue
         if triplets:
             pool = ClipPool.from_files(paths, int(audio_cfg["sample_rate"]), args.device, resample=args.resample, normalize=args.normalize)
-            written = write_dataset(pool, triplets, numbers, out, audio_cfg, c.audio["audio_len"], form, args.batch, encoder)
+            written = write_dataset(pool, triplets, numbers, out, audio_cfg, c.audio["audio_len"], form, args.batch, encoder,
+                                    reverb_arguments(args, int(audio_cfg["sample_rate"]), args.device, args.seed))
         print(f"{name}: {written} triplets written to {out}, {len(triplets) - written} too short or silent, "
               f"{skipped} skipped for a missing file")
 

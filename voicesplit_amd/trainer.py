@@ -860,8 +860,10 @@ def _mixture_batches(args, c, acfg, b, rank, world, dev):
         print(f"{len(kept)} triplets from {len(pool)} clips ({pool.total / acfg['sample_rate'] / 3600:.2f} h on the device); "
               f"{len(numbers) - len(kept)} dropped (too short, silent or without an embedding), {skipped} skipped for a missing file", flush=True)
     shard = EpochShard(len(kept), b, rank, world, c.train_config["seed"])
+    reverb = mixing.reverb_arguments(args, int(acfg["sample_rate"]), dev, c.train_config["seed"]) if hasattr(args, "reverb_rooms") else None
+    reverb = {k: v for k, v in (reverb or {}).items() if k != "seed"}
     return mixing.MixtureBatches(pool, kept, table, acfg, c.audio["audio_len"], shard, crop=args.mix_crop,
-                                 seed=c.train_config["seed"], emb_rows=rows)
+                                 seed=c.train_config["seed"], emb_rows=rows, **reverb)
 
 
 def _overlay_batches(args, c, acfg, b, rank, world, dev, pool, triplets, numbers):
@@ -928,9 +930,13 @@ def main(argv=None):
     ap.add_argument("--noise-csv", default=None, help="--no-overlay: one noise file per line, relative to --mix-root")
     ap.add_argument("--emb-dir", default=None, help="precomputed %%06d-emb.pt per CSV row, instead of embedding the reference clips here")
     ap.add_argument("--speaker-checkpoint", default=None, help="embedder.pt of the GE2E speaker encoder (--mix-csv without --emb-dir)")
+    from .mixing import add_reverb_arguments
+    add_reverb_arguments(ap)
     args = ap.parse_args(argv)
     if args.no_overlay != bool(args.noise_csv) or (args.no_overlay and not args.mix_csv):
         ap.error("--no-overlay, --noise-csv and --mix-csv go together")
+    if (args.reverb_rooms or args.sir_db) and (not args.mix_csv or args.no_overlay):
+        ap.error("--reverb-rooms and --sir-db need --mix-csv, without --no-overlay")
     c = load_config(args.config_path)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
