@@ -44,6 +44,29 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class Built:
+    """The order between the stream that built device data and the streams that read it later.  An object that fills a device buffer
+    once and keeps it past the call (a resampler's tap bank, prepared weights, a pool of room responses) makes one of these right
+    behind the launches that fill the buffer -- it records an event on the building stream -- and calls ``wait()`` in front of every
+    use: the stream current at that moment waits for the event on the device; the host never blocks.  Once the event has completed
+    it is dropped, and ``wait()`` costs one attribute test from then on."""
+    __slots__ = ("_event", "_device")
+
+    def __init__(self, device):
+        self._device = torch.device(device)
+        self._event = torch.cuda.Event()
+        self._event.record(torch.cuda.current_stream(self._device))
+
+    def wait(self):
+        ev = self._event
+        if ev is None:
+            return
+        if ev.query():
+            self._event = None
+        else:
+            torch.cuda.current_stream(self._device).wait_event(ev)
+
+
 def call(name: str, device, *args, what: Optional[str] = None):
     """``vs_<name>(*args, stream)`` with ``device`` current, on that device's current stream; tensors go down as their data pointer,
     None as NULL, everything else as it is.  Raises VoiceSplitHipError (labelled ``what``, default the symbol) on a non-zero rc."""

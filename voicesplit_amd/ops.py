@@ -133,7 +133,9 @@ class PreparedWeights:
     """What an eval-mode forward derives from the parameters alone (vs_prepare_weights), kept on the device
     together with the identity of the tensors it was derived from: ``matches(sd, dims)`` is False as soon as
     any parameter / BatchNorm buffer was replaced or modified in place (optimizer step, load_state_dict,
-    ``.to()``), or the arithmetic changed."""
+    ``.to()``), or the arithmetic changed.  The buffer is filled on the stream current at construction; ``forward_prepared`` and
+    ``forward_prepared_multi`` make their own stream wait for that on the device (``_call.Built``), so the weights may be prepared
+    under one stream and used under any other."""
 
     def __init__(self, sd, dims: VsDims):
         some = next(iter(sd.values()))
@@ -141,6 +143,7 @@ class PreparedWeights:
         self.key = self._key(sd, dims)
         params = pack_params(sd)
         _call.call("prepare_weights", some.device, ctypes.byref(dims), ctypes.byref(params), self.buf, self.buf.numel())
+        self.built = _call.Built(some.device)
 
     @staticmethod
     def _key(sd, dims: VsDims):
@@ -172,6 +175,7 @@ def forward_prepared(sd, prepared: PreparedWeights, x, dvec, dims: VsDims, conv_
     params = pack_params(sd)
     ws = workspace if workspace is not None else get_workspace(dims, x.device)
     mask = torch.empty(dims.B, dims.T, dims.FC2, dtype=torch.float32, device=x.device)
+    prepared.built.wait()
     lead = (ctypes.byref(dims), ctypes.byref(params), prepared.buf, prepared.buf.numel(), x, dvec)
     if lengths is not None:
         lens = device_lengths(lengths, dims.B, dims.T, x.device)
@@ -204,6 +208,7 @@ def forward_prepared_multi(sd, prepared: PreparedWeights, x, dvecs, dims: VsDims
     ws = workspace if workspace is not None else get_multi_workspace(dims, K, x.device)
     lens = device_lengths(lengths, dims.B, dims.T, x.device) if lengths is not None else None
     mask = torch.empty(dims.B, K, dims.T, dims.FC2, dtype=torch.float32, device=x.device)
+    prepared.built.wait()
     _call.call("forward_prepared_multi", x.device, ctypes.byref(dims), ctypes.byref(params), prepared.buf, prepared.buf.numel(),
                x, dvecs, K, lens, ACT_CODES[conv_act], ws, ws.numel(), mask)
     return mask

@@ -47,7 +47,9 @@ def first_needed(d: _lib.VsResampleDims, n: int) -> int:
 
 
 class Resampler:
-    """One pair of rates on one device: the polyphase bank (built once by ``vs_resample_bank``) and the calls that use it."""
+    """One pair of rates on one device: the polyphase bank (built once by ``vs_resample_bank``) and the calls that use it.  The bank
+    is filled on the stream current at construction; every call that reads it makes its own stream wait for that on the device
+    (``_call.Built``), so an instance may be built under one stream and used under any other."""
 
     def __init__(self, sr_in: int, sr_out: int, device="cuda:0"):
         self.dims = plan(sr_in, sr_out)
@@ -59,6 +61,7 @@ class Resampler:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.bank = torch.empty(self.dims.L * self.dims.T, dtype=torch.float32, device=self.device)
         _call.call("resample_bank", self.device, ctypes.byref(self.dims), self.bank)
+        self._built = _call.Built(self.device)
 
     def out_len(self, n_in: int) -> int:
         return out_len(self.dims, n_in)
@@ -83,6 +86,7 @@ class Resampler:
         out = self._rows(out, "out")
         if out.shape != (B, int(y_count)):
             raise ValueError(f"out: expected [{B}, {y_count}], got {tuple(out.shape)}")
+        self._built.wait()
         _call.call("resample", self.device, ctypes.byref(self.dims), self.bank, buf, int(x_first), buf.shape[1], buf.stride(0),
                    int(stream_len), out, int(y_first), int(y_count), out.stride(0), B)
         return out
@@ -104,6 +108,7 @@ class Resampler:
             raise ValueError("table: expected [N, 3] int64 on the host")
         table = table.contiguous()
         table_dev = table.to(self.device)
+        self._built.wait()
         _call.call("resample_clips", self.device, ctypes.byref(self.dims), self.bank, flat_in, flat_in.numel(), out, out.numel(),
                    table, table_dev, table.shape[0])
 

@@ -216,7 +216,9 @@ class RirPool:
     """The responses of R drawn rooms resident on one device: ``h`` [2 R, H] fp32, ``nh`` [2 R] int32 (device; ``nh_host`` on the
     host), ``nh_early`` the taps of the response cut 50 ms behind the direct path, ``rooms`` the table [2 R, 19] and ``rt60`` [R].
     Response 2 r is room r's target source, 2 r + 1 its interferer.  The rooms come from a generator of their own, seeded from
-    (seed, epoch); ``redraw(epoch)`` makes a fresh pool with the same settings."""
+    (seed, epoch); ``redraw(epoch)`` makes a fresh pool with the same settings.  The device tensors are filled on the stream
+    current at construction (and at ``redraw``); reading ``h``, ``nh`` or ``nh_early`` makes the stream current at that moment wait
+    for that on the device (``_call.Built``), so a pool may be drawn under one stream and used under any other."""
 
     def __init__(self, R: int, device="cuda:0", seed: int = 0, epoch: int = 0, **draw):
         from .mixing import crop_seed
@@ -225,11 +227,23 @@ class RirPool:
         rooms, rt60 = draw_rooms(self.R, g, **draw)
         self._adopt(rooms, rt60, shoebox_rir(rooms, device))
 
+    def _resident(self, h, nh, nh_early):
+        self._h, self._nh, self._nh_early, self.device = h, nh, nh_early, h.device
+        self._built = _call.Built(h.device)
+
+    def _ordered(self, t):
+        self._built.wait()
+        return t
+
+    h = property(lambda self: self._ordered(self._h))
+    nh = property(lambda self: self._ordered(self._nh))
+    nh_early = property(lambda self: self._ordered(self._nh_early))
+
     def _adopt(self, rooms, rt60, h):
-        self.rooms, self.rt60, self.h, self.device = rooms, rt60, h, h.device
+        self.rooms, self.rt60 = rooms, rt60
         self.nh_host = rooms[:, _COL["nh"]].to(torch.int32)
         self.nh_early_host = early_taps(rooms)
-        self.nh, self.nh_early = self.nh_host.to(h.device), self.nh_early_host.to(h.device)
+        self._resident(h, self.nh_host.to(h.device), self.nh_early_host.to(h.device))
 
     @classmethod
     def from_rooms(cls, rooms: torch.Tensor, device="cuda:0") -> "RirPool":
@@ -247,10 +261,9 @@ class RirPool:
         self = cls.__new__(cls)
         self.R, self.seed, self.epoch, self.draw = 1, 0, 0, None
         self.rooms = self.rt60 = None
-        self.h = torch.ones(2, 1, dtype=torch.float32, device=_device(device))
-        self.device = self.h.device
         self.nh_host = self.nh_early_host = torch.ones(2, dtype=torch.int32)
-        self.nh = self.nh_early = self.nh_host.to(self.device)
+        nh = self.nh_host.to(_device(device))
+        self._resident(torch.ones(2, 1, dtype=torch.float32, device=nh.device), nh, nh)
         return self
 
     def __len__(self) -> int:

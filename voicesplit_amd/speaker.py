@@ -118,7 +118,9 @@ class LinearNorm(nn.Module):
 
 class SpeakerEncoder(nn.Module):
     """The notebook's encoder: 3-layer LSTM(40 -> 768) over sliding windows of 80 mel frames (stride 40), last frame,
-    Linear(768 -> 256), L2 normalisation per window, mean over the windows."""
+    Linear(768 -> 256), L2 normalisation per window, mean over the windows.  The packed weights are built once per set of
+    parameters, on the stream current at that moment; every later use makes its own stream wait for that on the device
+    (``_call.Built``), so the encoder may be prepared under one stream and used under any other."""
 
     _TRANSIENT = ("_prepared",)
 
@@ -165,6 +167,7 @@ class SpeakerEncoder(nn.Module):
         key = (self.math,) + tuple((p.data_ptr(), p._version) for p in ps)
         prep = self.__dict__.get("_prepared")
         if prep is not None and prep[0] == key:
+            prep[2].wait()
             return prep[1]
         d = self._dims()
         buf = torch.empty(_call.sized("speaker_prepared_bytes", ctypes.byref(d)), dtype=torch.uint8, device=device)
@@ -173,7 +176,7 @@ class SpeakerEncoder(nn.Module):
             sp.w_ih[k], sp.w_hh[k], sp.b_ih[k], sp.b_hh[k] = (p.data_ptr() for p in ps[4 * k:4 * k + 4])
         sp.proj_w, sp.proj_b = ps[-2].data_ptr(), ps[-1].data_ptr()
         _call.call("speaker_prepare", device, ctypes.byref(d), ctypes.byref(sp), buf, buf.numel())
-        self.__dict__["_prepared"] = (key, buf)
+        self.__dict__["_prepared"] = (key, buf, _call.Built(device))
         return buf
 
     @torch.no_grad()
