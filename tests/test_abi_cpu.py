@@ -100,6 +100,94 @@ def test_workspace_layout_and_argument_errors():
     assert lib.vs_lstm_state_floats(3, 24) == 4 * 2 * 32 * 32 + 64 and lib.vs_lstm_state_floats(64, 400) == 4 * 2 * 400 * 64 + 64
 
 
+def test_gemm_entry_points_refuse_bad_descriptors_before_any_launch():
+    """Every refusal of the GEMM checks that the exported calls can reach, one call per condition, over aligned fake pointers:
+    each is refused before a launch, with the message of its kernel's prefix (gemm:, gemm_f16x3:, gemm_bf16:)."""
+    from voicesplit_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)
+    NONE, MISH = 2, 1
+
+    def refused(rc, fragment):
+        assert rc != 0 and fragment in lib.vs_last_error(), (rc, fragment, lib.vs_last_error())
+
+    def gemm(split=False, **kw):
+        a = dict(la=0, lw=0, lda=32, ldw=32, ldc=24, M=16, N=24, K=32, bias=None, gate=None, ldg=0, a_relu=0, w_relu=0, act=NONE, acc=0,
+                 w_shift=0, w_group=0, splits=1, partials=None)
+        a.update(kw)
+        head = (a["la"], a["lw"], p, a["lda"], p, a["ldw"], p, a["ldc"], a["M"], a["N"], a["K"], a["bias"], a["gate"], a["ldg"],
+                a["a_relu"], a["w_relu"], a["act"], a["acc"])
+        if split:
+            return lib.vs_gemm_f16x3(*head, p, None)
+        return lib.vs_gemm(*head, a["w_shift"], a["w_group"], a["splits"], a["partials"], None)
+
+    # the checks both kernels share, under either prefix.  (vs_gemm_f16x3 with a bad shape: refused before its two scale passes)
+    for split, pre in ((False, b"gemm: "), (True, b"gemm_f16x3: ")):
+        refused(gemm(split, M=0), pre + b"bad shape")
+        refused(gemm(split, N=-1), pre + b"bad shape")
+        refused(gemm(split, la=2), pre + b"bad layout")
+        refused(gemm(split, lw=-1), pre + b"bad layout")
+        refused(gemm(split, lda=31), pre + b"leading dims")                 # K-contiguous A: lda >= K
+        refused(gemm(split, la=1, lda=15), pre + b"leading dims")           # K-major A: lda >= M
+        refused(gemm(split, ldw=31), pre + b"leading dims")                 # K-contiguous W: ldw >= K
+        refused(gemm(split, lw=1, ldw=23), pre + b"leading dims")           # K-major W: ldw >= N
+        refused(gemm(split, ldc=23), pre + b"leading dims")
+        refused(gemm(split, gate=p, ldg=23), pre + b"gate needs ldg>=N")
+        refused(gemm(split, act=MISH), pre + b"unsupported activation 1")
+    # the fp32 kernel's own
+    refused(gemm(M=65535 * 128 + 1), b"gemm: M=8388481 too large")
+    refused(gemm(w_group=4, w_shift=1), b"gemm: w_shift/w_group need the K-major W layout")
+    splitk = b"gemm: split-K needs a partial buffer, a dense C and no epilogue terms"
+    refused(gemm(splits=2, partials=p, bias=p), splitk)
+    refused(gemm(splits=2, partials=p, gate=p, ldg=24), splitk)
+    refused(gemm(splits=2, partials=p, acc=1), splitk)
+    refused(gemm(splits=2, partials=p, act=0), splitk)
+    refused(gemm(splits=2, partials=p, ldc=32), splitk)
+    refused(gemm(splits=2), splitk)                                         # NULL partials
+    refused(lib.vs_gemm(0, 0, None, 32, p, 32, p, 24, 16, 24, 32, None, None, 0, 0, 0, NONE, 0, 0, 0, 1, None, None), b"gemm: NULL argument")
+    # the split kernel's own: 32-bit offsets of its operands, its tile raster
+    refused(gemm(True, la=1, lda=1 << 30, K=2, ldw=2), b"gemm_f16x3: K-major A above 4 GiB")
+    refused(gemm(True, lw=1, ldw=1 << 30, K=2, lda=2), b"gemm_f16x3: K-major W above 4 GiB")
+    refused(gemm(True, lda=1 << 30), b"gemm_f16x3: A above 4 GiB")
+    refused(gemm(True, ldw=1 << 30), b"gemm_f16x3: W above 4 GiB")
+    refused(gemm(True, M=1 << 22, N=1 << 22, K=1, lda=1, ldw=1, ldc=1 << 22), b"gemm_f16x3: too many tiles")
+    refused(lib.vs_gemm_f16x3(0, 0, p, 32, p, 32, p, 24, 16, 24, 32, None, None, 0, 0, 0, NONE, 0, None, None), b"gemm_f16x3: NULL argument")
+
+    # the row bias is reachable through vs_gemm_nt
+    def gemm_nt(**kw):
+        a = dict(M=16, N=24, K=32, ldrb=24, group=4)
+        a.update(kw)
+        return lib.vs_gemm_nt(p, 32, p, 32, p, 24, a["M"], a["N"], a["K"], None, None, p, a["ldrb"], a["group"], 0, NONE, None)
+
+    refused(gemm_nt(group=0), b"gemm: rowbias needs group>0 and ldrb>=N")
+    refused(gemm_nt(ldrb=23), b"gemm: rowbias needs group>0 and ldrb>=N")
+    refused(gemm_nt(K=0), b"gemm: bad shape M=16 N=24 K=0")
+
+    # the bf16-operand kernel: operands [16][64] x [24][64] (row forms padded to 64 in k)
+    def gemm_bf16(**kw):
+        a = dict(ak=0, bk=0, A=p, lda=64, B=p, ldb=64, M=16, N=24, K=40, rowbias=None, ldrb=0, group=1)
+        a.update(kw)
+        return lib.vs_gemm_bf16(a["ak"], a["bk"], a["A"], a["lda"], a["B"], a["ldb"], p, 24, a["M"], a["N"], a["K"],
+                                a["rowbias"], a["ldrb"], a["group"], 0, None)
+
+    aligned = b"gemm_bf16: operands must be 16-byte aligned with ld a multiple of 8"
+    refused(gemm_bf16(M=0), b"gemm_bf16: bad argument")
+    refused(gemm_bf16(A=None), b"gemm_bf16: bad argument")
+    refused(gemm_bf16(A=ctypes.c_void_p(264)), aligned)
+    refused(gemm_bf16(B=ctypes.c_void_p(258)), aligned)
+    refused(gemm_bf16(lda=68), aligned)
+    refused(gemm_bf16(ldb=68), aligned)
+    refused(gemm_bf16(rowbias=p, ldrb=24, group=0), b"gemm_bf16: rowbias needs group > 0 and ldrb >= N")
+    refused(gemm_bf16(rowbias=p, ldrb=23, group=4), b"gemm_bf16: rowbias needs group > 0 and ldrb >= N")
+    refused(gemm_bf16(K=65), b"gemm_bf16: row-form A must be padded to a multiple of 64 in k")
+    refused(gemm_bf16(K=65, lda=128), b"gemm_bf16: row-form B must be padded to a multiple of 64 in k")
+    refused(gemm_bf16(ak=1, lda=16), b"gemm_bf16: the col x row form is not used by the path")
+    refused(lib.vs_gemm_bf16_gated(0, 0, p, 64, p, 64, p, 24, 16, 24, 40, p, 23, None), b"gemm_bf16: gate needs ldg >= N and a single output")
+    refused(lib.vs_gemm_bf16_gated(0, 0, p, 64, p, 68, p, 24, 16, 24, 40, p, 24, None), aligned)
+    refused(lib.vs_gemm_bf16_split(0, 0, p, 64, p, 64, p, p, 24, 8, 16, 24, 65, 0, None), b"gemm_bf16: row-form A must be padded")
+    refused(lib.vs_gemm_bf16_split(0, 0, p, 64, p, 64, p, p, 24, 8, 16, 0, 40, 0, None), b"gemm_bf16: bad argument")
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from voicesplit_amd import _lib
     with pytest.raises(_lib.VoiceSplitHipError, match="no PyTorch/CPU fallback"):

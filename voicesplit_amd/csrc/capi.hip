@@ -188,19 +188,23 @@ int vs_cvt_rows_bf16(const float* src, long long rows, int K, int ld, void* dst,
 
 int vs_gemm_bf16(int a_kmajor, int b_kmajor, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K,
                  const float* rowbias, int ldrb, int group, int accumulate, void* stream) {
-  return vs_gemm_bf16_impl(a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, nullptr, 0, M, N, K, rowbias, ldrb, group, accumulate, (hipStream_t)stream);
+  return vs_gemm_bf16_impl({.A = A, .lda = lda, .a_kmajor = a_kmajor, .B = B, .ldb = ldb, .b_kmajor = b_kmajor, .C = C, .ldc = ldc,
+                            .M = M, .N = N, .K = K, .rowbias = rowbias, .ldrb = ldrb, .group = group, .accumulate = accumulate},
+                           (hipStream_t)stream);
 }
 
 int vs_gemm_bf16_split(int a_kmajor, int b_kmajor, const void* A, int lda, const void* B, int ldb, float* C, float* C2, int ldc, int split_m,
                        int M, int N, int K, int accumulate, void* stream) {
   VS_REQUIRE(C2 && split_m > 0 && split_m < M, "gemm_bf16_split: needs C2 and 0 < split_m < M (split_m %d, M %d)", split_m, M);
-  return vs_gemm_bf16_impl(a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, C2, split_m, M, N, K, nullptr, 0, 1, accumulate, (hipStream_t)stream);
+  return vs_gemm_bf16_impl({.A = A, .lda = lda, .a_kmajor = a_kmajor, .B = B, .ldb = ldb, .b_kmajor = b_kmajor, .C = C, .ldc = ldc,
+                            .C2 = C2, .split_m = split_m, .M = M, .N = N, .K = K, .accumulate = accumulate}, (hipStream_t)stream);
 }
 
 int vs_gemm_bf16_gated(int a_kmajor, int b_kmajor, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K,
                        const float* gate, int ldg, void* stream) {
   VS_REQUIRE(gate != nullptr, "gemm_bf16_gated: gate is NULL");
-  return vs_gemm_bf16_impl(a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, nullptr, 0, M, N, K, nullptr, 0, 1, 0, (hipStream_t)stream, gate, ldg);
+  return vs_gemm_bf16_impl({.A = A, .lda = lda, .a_kmajor = a_kmajor, .B = B, .ldb = ldb, .b_kmajor = b_kmajor, .C = C, .ldc = ldc,
+                            .M = M, .N = N, .K = K, .gate = gate, .ldg = ldg}, (hipStream_t)stream);
 }
 
 int vs_nhwc_conv_first(const float* x, const float* w, const float* scale, const float* shift, void* out,
@@ -318,7 +322,8 @@ int vs_conv_last_fwd(const float* in, const float* w, const float* scale, const 
 int vs_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
                const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
                int a_relu, int act, void* stream) {
-  return vs_gemm_nt_impl(A, lda, W, ldw, C, ldc, M, N, K, bias1, bias2, rowbias, ldrb, group, a_relu, act, (hipStream_t)stream);
+  return vs_gemm_impl({.A = A, .lda = lda, .a_relu = a_relu, .W = W, .ldw = ldw, .C = C, .ldc = ldc, .M = M, .N = N, .K = K,
+                       .bias1 = bias1, .bias2 = bias2, .rowbias = rowbias, .ldrb = ldrb, .group = group, .act = act}, (hipStream_t)stream);
 }
 
 int vs_lstm_pack(const float* w_hh_fwd, const float* w_hh_bwd, float* packed, int H, void* stream) {
@@ -418,8 +423,9 @@ int vs_gemm(int layout_a, int layout_w, const float* A, int lda, const float* W,
             int M, int N, int K, const float* bias, const float* gate, int ldg, int a_relu, int w_relu, int act,
             int accumulate, int w_shift, int w_group, int splits, float* partials, void* stream) {
   VS_REQUIRE(A && W && C, "gemm: NULL argument");
-  return vs_gemm_general_impl(layout_a, layout_w, A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, K, bias, nullptr, nullptr, 0, 1,
-                              gate, ldg, a_relu, w_relu, act, accumulate, w_shift, w_group, splits, partials, (hipStream_t)stream);
+  return vs_gemm_impl({.A = A, .lda = lda, .a_kmajor = layout_a, .a_relu = a_relu, .W = W, .ldw = ldw, .w_kmajor = layout_w, .w_relu = w_relu,
+                       .C = C, .ldc = ldc, .accumulate = accumulate, .M = M, .N = N, .K = K, .bias1 = bias, .gate = gate, .ldg = ldg,
+                       .act = act, .w_shift = w_shift, .w_group = w_group, .splits = splits, .partials = partials}, (hipStream_t)stream);
 }
 
 int vs_gemm_f16x3(int layout_a, int layout_w, const float* A, int lda, const float* W, int ldw, float* C, int ldc,
@@ -427,12 +433,15 @@ int vs_gemm_f16x3(int layout_a, int layout_w, const float* A, int lda, const flo
                   int accumulate, float* scratch8, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   VS_REQUIRE(A && W && C && scratch8, "gemm_f16x3: NULL argument");
+  const VsGemm g{.arith = VS_GEMM_SPLIT_F16, .A = A, .lda = lda, .a_kmajor = layout_a, .a_relu = a_relu, .W = W, .ldw = ldw,
+                 .w_kmajor = layout_w, .w_relu = w_relu, .C = C, .ldc = ldc, .accumulate = accumulate, .M = M, .N = N, .K = K, .bias1 = bias,
+                 .gate = gate, .ldg = ldg, .act = act, .a_scale2 = scratch8, .w_scale2 = scratch8 + 2};
+  if (int rc = vs_gemm_check(g)) return rc;      // a bad descriptor is refused before anything is enqueued
   unsigned* amax = reinterpret_cast<unsigned*>(scratch8 + 4);
   // the operands are dense [rows][ld] buffers here: scale over the whole buffers
   if (int rc = vs_pow2_scale_impl(A, (long long)(layout_a ? K : M) * lda, amax, scratch8, stream)) return rc;
   if (int rc = vs_pow2_scale_impl(W, (long long)(layout_w ? K : N) * ldw, amax + 1, scratch8 + 2, stream)) return rc;
-  return vs_gemm_f16x3_impl(layout_a, layout_w, A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, K, bias, nullptr, nullptr, 0, 1,
-                            gate, ldg, a_relu, w_relu, act, accumulate, scratch8, scratch8 + 2, stream);
+  return vs_gemm_impl(g, stream);
 }
 
 int vs_bilstm_recurrent_train(const float* xg, const float* packed_whh, float* state, float* out, float* gates_save,

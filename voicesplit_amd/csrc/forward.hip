@@ -229,12 +229,13 @@ int vs_lstm_input_gemm_impl(int math, const float* feat, int K, const float* w_i
       if (int rc = vs_cvt_rows_bf16_impl(w_ih1, 4 * H, K, KE, base + Lb.wih + (size_t)4 * H * Lb.Kp * 2, Lb.Kp, stream)) return rc;
     }
     const void* wih = ready.wh ? static_cast<const void*>(ready.wh) : static_cast<const void*>(base + Lb.wih);
-    return vs_gemm_bf16_impl(0, 0, base + Lb.feat, Lb.Kp, wih, Lb.Kp, xg, 8 * H, nullptr, 0, M, 8 * H, K,
-                             rowbias, 8 * H, T, 0, stream);
+    return vs_gemm_bf16_impl({.A = base + Lb.feat, .lda = Lb.Kp, .B = wih, .ldb = Lb.Kp, .C = xg, .ldc = 8 * H, .M = M, .N = 8 * H, .K = K,
+                              .rowbias = rowbias, .ldrb = 8 * H, .group = T}, stream);
   }
-  if (math == VS_MATH_FP32)
-    return vs_gemm_nt2_impl(feat, K, w_ih0, w_ih1, 4 * H, KE, xg, 8 * H, M, 8 * H, K, nullptr, nullptr, rowbias, 8 * H, T, 0,
-                            VS_ACT_NONE, stream);
+  // x @ [W_ih; W_ih_reverse]^T converted from the fp32 tensors while staged: the fp32 kernel, or the split kernel with the scales below
+  VsGemm xw{.A = feat, .lda = K, .W = w_ih0, .ldw = KE, .W_hi = w_ih1, .n_split = 4 * H, .C = xg, .ldc = 8 * H, .M = M, .N = 8 * H, .K = K,
+            .rowbias = rowbias, .ldrb = 8 * H, .group = T};
+  if (math == VS_MATH_FP32) return vs_gemm_impl(xw, stream);
   // VS_MATH_BF16 without room for the bf16 operand copies: the split-operand GEMM re-derives its operands from the fp32 tensors.  A
   // prepared blob of this arithmetic holds W_ih as bf16 bits (no f16 halves, no scale) -- never to be read as the split form.
   const bool prepared = ready.wscale2 != nullptr && math != VS_MATH_BF16;
@@ -250,9 +251,12 @@ int vs_lstm_input_gemm_impl(int math, const float* feat, int K, const float* w_i
   if (!prepared) {
     if (int rc = vs_lstm_split_wih_impl(math, w_ih0, w_ih1, H, K, KE, amax + 1, gs + 2, presplit ? Wh : nullptr, Wl, stream)) return rc;
   }
-  if (!presplit)
-    return vs_gemm_f16x3_impl(0, 0, feat, K, w_ih0, w_ih1, 4 * H, KE, xg, 8 * H, M, 8 * H, K, nullptr, nullptr, rowbias, 8 * H, T,
-                              nullptr, 0, 0, 0, VS_ACT_NONE, 0, gs, wscale2, stream, math);
+  if (!presplit) {
+    xw.arith = math == VS_MATH_BF16 ? VS_GEMM_SPLIT_BF16 : VS_GEMM_SPLIT_F16;
+    xw.a_scale2 = gs;
+    xw.w_scale2 = wscale2;
+    return vs_gemm_impl(xw, stream);
+  }
   if (!ready.feat_rows) { if (int rc = vs_split_rows_impl(feat, M, K, K, gs, Ah, Al, 0, stream, math)) return rc; }
   return vs_gemm_presplit_impl(Ah, Al, prepared ? ready.wh : Wh, prepared ? ready.wl : Wl, S.Kp, xg, 8 * H, M, 8 * H, nullptr, nullptr,
                                rowbias, 8 * H, T, VS_ACT_NONE, 0, gs, wscale2, stream, math);
@@ -539,8 +543,8 @@ int bilstm(const Fwd& f, const float* feat, const float* dvec, float* lstm_out, 
       VS_REQUIRE(p->w_ih[dir] && p->w_hh[dir] && p->b_ih[dir] && p->b_hh[dir], "bilstm: NULL LSTM parameter (dir %d)", dir);
       // cat((x, dvec.repeat(T))) @ W_ih^T == x @ W_ih[:, :8F]^T + (dvec @ W_ih[:, 8F:]^T): the
       // second term does not depend on t -> one [B][4H] row bias per utterance (+ b_ih + b_hh).
-      if (int rc = vs_gemm_nt_impl(dvec, d->E, p->w_ih[dir] + K, KE, dvbias + (size_t)dir * 4 * H, 8 * H, NS, 4 * H, d->E,
-                                   p->b_ih[dir], p->b_hh[dir], nullptr, 0, 1, 0, VS_ACT_NONE, f.stream)) return rc;
+      if (int rc = vs_gemm_impl({.A = dvec, .lda = d->E, .W = p->w_ih[dir] + K, .ldw = KE, .C = dvbias + (size_t)dir * 4 * H, .ldc = 8 * H,
+                                 .M = NS, .N = 4 * H, .K = d->E, .bias1 = p->b_ih[dir], .bias2 = p->b_hh[dir]}, f.stream)) return rc;
     }
     // both directions in one launch (N = 8H): twice the workgroups, half the tail quantisation.  multi: the K speakers of a mixture
     // share its gate pre-activations, so the big GEMM runs once per mixture WITHOUT the row bias; the shared-input recurrence adds each
@@ -591,15 +595,18 @@ int head(const Fwd& f, const float* lstm_out, float* logits, float* mask) {
     if (img) return vs_head_fused_impl(lstm_out, img, nullptr, logits, mask, M, 2 * d->H, d->FC1, d->FC2, f.stream);
   }
   // VS_MATH_BF16: bf16-rounded operands on the bf16 matrix instruction, fp32 accumulate and epilogue
-  const auto gemm_nt = d->math == VS_MATH_BF16 ? vs_gemm_nt_bf16_impl : vs_gemm_nt_impl;
+  const VsGemmArith arith = d->math == VS_MATH_BF16 ? VS_GEMM_FP32_BF16 : VS_GEMM_FP32;
   // relu(lstm) -> fc1 -> relu
-  if (int rc = gemm_nt(lstm_out, 2 * d->H, p->fc1_w, 2 * d->H, h1, d->FC1, M, d->FC1, 2 * d->H, p->fc1_b, nullptr, nullptr, 0, 1, 1, VS_ACT_RELU, f.stream)) return rc;
+  if (int rc = vs_gemm_impl({.arith = arith, .A = lstm_out, .lda = 2 * d->H, .a_relu = 1, .W = p->fc1_w, .ldw = 2 * d->H, .C = h1, .ldc = d->FC1,
+                             .M = M, .N = d->FC1, .K = 2 * d->H, .bias1 = p->fc1_b, .act = VS_ACT_RELU}, f.stream)) return rc;
   // fc2 -> sigmoid
-  if (logits) {
-    if (int rc = gemm_nt(h1, d->FC1, p->fc2_w, d->FC1, logits, d->FC2, M, d->FC2, d->FC1, p->fc2_b, nullptr, nullptr, 0, 1, 0, VS_ACT_NONE, f.stream)) return rc;
-  }
+  VsGemm fc2{.arith = arith, .A = h1, .lda = d->FC1, .W = p->fc2_w, .ldw = d->FC1, .C = logits, .ldc = d->FC2,
+             .M = M, .N = d->FC2, .K = d->FC1, .bias1 = p->fc2_b};
+  if (logits) { if (int rc = vs_gemm_impl(fc2, f.stream)) return rc; }
   if (!mask) return 0;
-  return gemm_nt(h1, d->FC1, p->fc2_w, d->FC1, mask, d->FC2, M, d->FC2, d->FC1, p->fc2_b, nullptr, nullptr, 0, 1, 0, VS_ACT_SIGMOID, f.stream);
+  fc2.C = mask;
+  fc2.act = VS_ACT_SIGMOID;
+  return vs_gemm_impl(fc2, f.stream);
 }
 
 // ---- the whole path: what every vs_forward* runs behind its own validation ----

@@ -670,13 +670,13 @@ int vs_cvt_rows_bf16_impl(const float* src, long long rows, int K, int ld, void*
   return 0;
 }
 
-// C[M][N] (+)= opA(A) opB(B) + rowbias[m / group][n]; a_kmajor / b_kmajor: 0 = element (i, k) at i*ld + k, 1 = at k*ld + i.
-// Operands bf16, 16-byte aligned, ld a multiple of 8; row-form operands must be readable (zero padded) up to the next
-// multiple of 64 in k.  C2 / split_m: rows >= split_m are written to C2 (two output matrices stacked along M).
-// gate [M][ldg] (or NULL): elements where gate <= 0 are written as 0 (the relu mask of the head's backward contractions).
-int vs_gemm_bf16_impl(int a_kmajor, int b_kmajor, const void* A, int lda, const void* B, int ldb, float* C, int ldc, float* C2, int split_m,
-                      int M, int N, int K, const float* rowbias, int ldrb, int group, int accumulate, hipStream_t stream,
-                      const float* gate, int ldg) {
+// The contract is at VsGemmBf16 (vs_internal.h)
+int vs_gemm_bf16_impl(const VsGemmBf16& d, hipStream_t stream) {
+  const void *A = d.A, *B = d.B;
+  float *C = d.C, *C2 = d.C2;
+  const float *rowbias = d.rowbias, *gate = d.gate;
+  const int a_kmajor = d.a_kmajor, b_kmajor = d.b_kmajor, lda = d.lda, ldb = d.ldb, ldc = d.ldc, split_m = d.split_m, M = d.M, N = d.N, K = d.K;
+  const int ldrb = d.ldrb, group = d.group, accumulate = d.accumulate, ldg = d.ldg;
   VS_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, "gemm_bf16: bad argument");
   VS_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0,
              "gemm_bf16: operands must be 16-byte aligned with ld a multiple of 8");

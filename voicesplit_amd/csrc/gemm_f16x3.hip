@@ -489,44 +489,35 @@ void gemm_pre_kernel(GemmPreArgs g) {
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int gemm_band() { return 8; }      // tile rows per band of the raster (1 / 8 / 1024 measured the same in round 3: profiles/r03_gemm_l2_prefetch.md)
 
 }  // namespace
 
 int vs_pow2_scale_impl(const float* x, long long n, unsigned* amax_scratch, float* scale2, hipStream_t stream);
 
-// Same contract as vs_gemm_general_impl (no split-K, no w_shift).  a_scale2 / w_scale2: {s, 1/s}
-// of the two operands (see vs_pow2_scale_impl); the caller derives them once per tensor.
-int vs_gemm_f16x3_impl(int layout_a, int layout_w, const float* A, int lda, const float* W, const float* W_hi,
-                       int n_split, int ldw, float* C, int ldc, int M, int N, int K,
-                       const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                       const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
-                       const float* a_scale2, const float* w_scale2, hipStream_t stream, int math) {
-  const bool bf = math == VS_MATH_CODE_BF16;
-  VS_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_f16x3: bad shape M=%d N=%d K=%d", M, N, K);
-  VS_REQUIRE((layout_a == 0 || layout_a == 1) && (layout_w == 0 || layout_w == 1), "gemm_f16x3: bad layout");
-  VS_REQUIRE(lda >= (layout_a ? M : K) && ldw >= (layout_w ? N : K) && ldc >= N,
-             "gemm_f16x3: leading dims lda=%d ldw=%d ldc=%d vs M=%d N=%d K=%d", lda, ldw, ldc, M, N, K);
-  VS_REQUIRE(!rowbias || (group > 0 && ldrb >= N), "gemm_f16x3: rowbias needs group>0 and ldrb>=N");
-  VS_REQUIRE(!gate || ldg >= N, "gemm_f16x3: gate needs ldg>=N");
-  VS_REQUIRE(act == VS_ACT_NONE || act == VS_ACT_RELU || act == VS_ACT_SIGMOID, "gemm_f16x3: unsupported activation %d", act);
-  VS_REQUIRE(layout_w == 0 || (W_hi == nullptr || n_split >= N), "gemm_f16x3: stacked W needs the K-contiguous layout");
-  VS_REQUIRE(n_split >= N || W_hi != nullptr, "gemm_f16x3: W_hi is NULL but n_split=%d < N=%d", n_split, N);
-  VS_REQUIRE(a_scale2 && w_scale2, "gemm_f16x3: NULL scale");
-  VS_REQUIRE(!layout_a || ((size_t)(K - 1) * lda + M) * 4 < (1ull << 32), "gemm_f16x3: K-major A above 4 GiB");
-  VS_REQUIRE(!layout_w || ((size_t)(K - 1) * ldw + N) * 4 < (1ull << 32), "gemm_f16x3: K-major W above 4 GiB");
-  Gemm16Args g{A, lda, W, ldw, W_hi, n_split, C, ldc, M, N, K, bias1, bias2, rowbias, ldrb, group > 0 ? group : 1,
-               gate, ldg, a_relu, w_relu, act, accumulate, a_scale2, w_scale2, (M + BM - 1) / BM, (N + BN - 1) / BN, gemm_band()};
-  const bool vec = (lda % 4 == 0) && (ldw % 4 == 0) && (K % 4 == 0) && aligned16(A) && aligned16(W) && aligned16(W_hi);
-  VS_REQUIRE(layout_a || ((size_t)(M - 1) * lda + K) * 4 < (1ull << 32) - 64, "gemm_f16x3: A above 4 GiB");
-  VS_REQUIRE(layout_w || ((size_t)(N - 1) * ldw + K) * 4 < (1ull << 32) - 64, "gemm_f16x3: W above 4 GiB");
-  VS_REQUIRE((long long)g.tiles_m * g.tiles_n < (1LL << 30), "gemm_f16x3: too many tiles");
+// The split kernel behind vs_gemm_impl (which has made the checks both kernels share): its own refusals, then its launch.
+// a_scale2 / w_scale2: {s, 1/s} of the two operands (see vs_pow2_scale_impl); the caller derives them once per tensor.
+int vs_gemm_f16x3_check(const VsGemm& g) {
+  VS_REQUIRE(g.splits <= 1 && g.w_group == 0, "gemm_f16x3: no split-K and no w_shift/w_group on the split kernel");
+  VS_REQUIRE(g.a_scale2 && g.w_scale2, "gemm_f16x3: NULL scale");
+  VS_REQUIRE(!g.a_kmajor || ((size_t)(g.K - 1) * g.lda + g.M) * 4 < (1ull << 32), "gemm_f16x3: K-major A above 4 GiB");
+  VS_REQUIRE(!g.w_kmajor || ((size_t)(g.K - 1) * g.ldw + g.N) * 4 < (1ull << 32), "gemm_f16x3: K-major W above 4 GiB");
+  VS_REQUIRE(g.a_kmajor || ((size_t)(g.M - 1) * g.lda + g.K) * 4 < (1ull << 32) - 64, "gemm_f16x3: A above 4 GiB");
+  VS_REQUIRE(g.w_kmajor || ((size_t)(g.N - 1) * g.ldw + g.K) * 4 < (1ull << 32) - 64, "gemm_f16x3: W above 4 GiB");
+  VS_REQUIRE((long long)((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) < (1LL << 30), "gemm_f16x3: too many tiles");
+  return 0;
+}
+
+int vs_gemm_f16x3_launch(const VsGemm& d, hipStream_t stream) {
+  const bool bf = d.arith == VS_GEMM_SPLIT_BF16;
+  Gemm16Args g{d.A, d.lda, d.W, d.ldw, d.W_hi, d.n_split, d.C, d.ldc, d.M, d.N, d.K, d.bias1, d.bias2, d.rowbias, d.ldrb,
+               d.group > 0 ? d.group : 1, d.gate, d.ldg, d.a_relu, d.w_relu, d.act, d.accumulate, d.a_scale2, d.w_scale2,
+               (d.M + BM - 1) / BM, (d.N + BN - 1) / BN, gemm_band()};
+  const bool vec = (d.lda % 4 == 0) && (d.ldw % 4 == 0) && (d.K % 4 == 0) && vs_aligned16(d.A) && vs_aligned16(d.W) && vs_aligned16(d.W_hi);
   dim3 grid((unsigned)((g.tiles_m * g.tiles_n + 7) / 8 * 8));
-  if (layout_a == 0 && layout_w == 0) launch_layout<0, 0>(g, vec, grid, stream, bf);
-  else if (layout_a == 0 && layout_w == 1) launch_layout<0, 1>(g, vec, grid, stream, bf);
-  else if (layout_a == 1 && layout_w == 0) launch_layout<1, 0>(g, vec, grid, stream, bf);
+  if (d.a_kmajor == 0 && d.w_kmajor == 0) launch_layout<0, 0>(g, vec, grid, stream, bf);
+  else if (d.a_kmajor == 0 && d.w_kmajor == 1) launch_layout<0, 1>(g, vec, grid, stream, bf);
+  else if (d.a_kmajor == 1 && d.w_kmajor == 0) launch_layout<1, 0>(g, vec, grid, stream, bf);
   else launch_layout<1, 1>(g, vec, grid, stream, bf);
   VS_LAUNCH_CHECK();
   return 0;
@@ -560,7 +551,7 @@ int vs_gemm_presplit_impl(const _Float16* Ah, const _Float16* Al, const _Float16
   VS_REQUIRE(M > 0 && N > 0 && Kp > 0 && Kp % PBK == 0 && ldc >= N, "gemm_presplit: bad shape M=%d N=%d Kp=%d ldc=%d", M, N, Kp, ldc);
   VS_REQUIRE(((size_t)M * Kp) * 2 < (1ull << 32) - 64 && ((size_t)N * Kp) * 2 < (1ull << 32) - 64, "gemm_presplit: operand above 4 GiB");
   VS_REQUIRE(!rowbias || (group > 0 && ldrb >= N), "gemm_presplit: rowbias needs group>0 and ldrb>=N");
-  VS_REQUIRE(aligned16(Ah) && aligned16(Al) && aligned16(Wh) && aligned16(Wl), "gemm_presplit: operands must be 16-byte aligned");
+  VS_REQUIRE(vs_aligned16(Ah) && vs_aligned16(Al) && vs_aligned16(Wh) && vs_aligned16(Wl), "gemm_presplit: operands must be 16-byte aligned");
   GemmPreArgs g{Ah, Al, Wh, Wl, C, ldc, M, N, Kp, bias1, bias2, rowbias, ldrb, group > 0 ? group : 1, act, accumulate,
                 a_scale2, w_scale2, (M + BM - 1) / BM, (N + BN - 1) / BN, gemm_band()};
   if (math == VS_MATH_CODE_BF16) hipLaunchKernelGGL(gemm_pre_kernel<true>, dim3((unsigned)((g.tiles_m * g.tiles_n + 7) / 8 * 8)), dim3(256), 0, stream, g);

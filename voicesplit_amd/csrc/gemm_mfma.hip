@@ -22,7 +22,7 @@
 // k per lane half) is one conflict-free ds_read_b128 feeding four K-steps.  Col-layout operands
 // stay K-major in LDS ([k][132]) and are read with ds_read_b32 (lanes = 32 consecutive rows:
 // conflict-free); the k -> (K-step, lane half) mapping is the same for both so they can be mixed.
-#include "vs_common.h"
+#include "vs_internal.h"
 
 namespace {
 
@@ -253,8 +253,6 @@ void launch_layout(const GemmArgs& g, bool vec, bool bf, dim3 grid, hipStream_t 
   else hipLaunchKernelGGL((gemm_kernel<LA, LB, false>), grid, dim3(256), 0, stream, g);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 __global__ void splitk_reduce_kernel(const float* __restrict__ part, int S, long long n, float* __restrict__ out) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
@@ -265,89 +263,63 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, int S, long
 
 }  // namespace
 
-// General entry.  layout_a / layout_w: 0 = K contiguous (A[m][k], W[n][k]); 1 = K-major
-// (A[k][m], W[k][n]).  splits > 1: split-K through `partials` ([splits][M][N] floats), summed in
-// a fixed order into C (which must then be dense, ldc == N, and take no epilogue terms).
-static int gemm_general(bool bf, int layout_a, int layout_w, const float* A, int lda, const float* W, const float* W_hi,
-                        int n_split, int ldw, float* C, int ldc, int M, int N, int K,
-                        const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                        const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
-                        int w_shift, int w_group, int splits, float* partials, hipStream_t stream) {
-  VS_REQUIRE(M > 0 && N > 0 && K > 0, "gemm: bad shape M=%d N=%d K=%d", M, N, K);
-  VS_REQUIRE((layout_a == 0 || layout_a == 1) && (layout_w == 0 || layout_w == 1), "gemm: bad layout");
-  VS_REQUIRE(lda >= (layout_a ? M : K) && ldw >= (layout_w ? N : K) && ldc >= N,
-             "gemm: leading dims lda=%d ldw=%d ldc=%d vs M=%d N=%d K=%d", lda, ldw, ldc, M, N, K);
-  VS_REQUIRE(!rowbias || (group > 0 && ldrb >= N), "gemm: rowbias needs group>0 and ldrb>=N");
-  VS_REQUIRE(!gate || ldg >= N, "gemm: gate needs ldg>=N");
-  VS_REQUIRE((M + BM - 1) / BM <= 65535, "gemm: M=%d too large", M);
-  VS_REQUIRE(act == VS_ACT_NONE || act == VS_ACT_RELU || act == VS_ACT_SIGMOID, "gemm: unsupported activation %d", act);
-  VS_REQUIRE(layout_w == 0 || (W_hi == nullptr || n_split >= N), "gemm: stacked W needs the K-contiguous layout");
-  VS_REQUIRE(n_split >= N || W_hi != nullptr, "gemm: W_hi is NULL but n_split=%d < N=%d", n_split, N);
-  VS_REQUIRE(w_group == 0 || layout_w == 1, "gemm: w_shift/w_group need the K-major W layout");
-  if (splits < 1) splits = 1;
-  int k_chunk = K;
-  if (splits > 1) {
-    VS_REQUIRE(partials != nullptr && ldc == N && !bias1 && !bias2 && !rowbias && !gate && act == VS_ACT_NONE && !accumulate,
-               "gemm: split-K needs a partial buffer, a dense C and no epilogue terms");
-    k_chunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
-    splits = (K + k_chunk - 1) / k_chunk;
+// The refusals both kernels share (what: "gemm" / "gemm_f16x3", the prefix of the messages)
+static int check_shared(const VsGemm& g, const char* what) {
+  VS_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "%s: bad shape M=%d N=%d K=%d", what, g.M, g.N, g.K);
+  VS_REQUIRE((g.a_kmajor == 0 || g.a_kmajor == 1) && (g.w_kmajor == 0 || g.w_kmajor == 1), "%s: bad layout", what);
+  VS_REQUIRE(g.lda >= (g.a_kmajor ? g.M : g.K) && g.ldw >= (g.w_kmajor ? g.N : g.K) && g.ldc >= g.N,
+             "%s: leading dims lda=%d ldw=%d ldc=%d vs M=%d N=%d K=%d", what, g.lda, g.ldw, g.ldc, g.M, g.N, g.K);
+  VS_REQUIRE(!g.rowbias || (g.group > 0 && g.ldrb >= g.N), "%s: rowbias needs group>0 and ldrb>=N", what);
+  VS_REQUIRE(!g.gate || g.ldg >= g.N, "%s: gate needs ldg>=N", what);
+  VS_REQUIRE(g.act == VS_ACT_NONE || g.act == VS_ACT_RELU || g.act == VS_ACT_SIGMOID, "%s: unsupported activation %d", what, g.act);
+  VS_REQUIRE(g.w_kmajor == 0 || (g.W_hi == nullptr || g.n_split >= g.N), "%s: stacked W needs the K-contiguous layout", what);
+  VS_REQUIRE(g.n_split >= g.N || g.W_hi != nullptr, "%s: W_hi is NULL but n_split=%d < N=%d", what, g.n_split, g.N);
+  return 0;
+}
+
+// the fp32 kernel's own: its grid limit in M, and what w_shift / w_group and split-K ask for
+static int check_fp32(const VsGemm& g) {
+  VS_REQUIRE((g.M + BM - 1) / BM <= 65535, "gemm: M=%d too large", g.M);
+  VS_REQUIRE(g.w_group == 0 || g.w_kmajor == 1, "gemm: w_shift/w_group need the K-major W layout");
+  VS_REQUIRE(g.splits <= 1 || (g.partials != nullptr && g.ldc == g.N && !g.bias1 && !g.bias2 && !g.rowbias && !g.gate &&
+                               g.act == VS_ACT_NONE && !g.accumulate),
+             "gemm: split-K needs a partial buffer, a dense C and no epilogue terms");
+  return 0;
+}
+
+static int launch_fp32(const VsGemm& d, hipStream_t stream) {
+  int splits = 1, k_chunk = d.K;
+  if (d.splits > 1) {
+    k_chunk = ((d.K + d.splits - 1) / d.splits + BK - 1) / BK * BK;
+    splits = (d.K + k_chunk - 1) / k_chunk;
   }
-  GemmArgs g{A, lda, W, ldw, W_hi, n_split, splits > 1 ? partials : C, ldc, M, N, K, bias1, bias2, rowbias, ldrb,
-             group > 0 ? group : 1, gate, ldg, a_relu, w_relu, act, accumulate, w_shift, w_group, k_chunk,
-             (long long)M * N};
-  const bool vec = (lda % 4 == 0) && (ldw % 4 == 0) && aligned16(A) && aligned16(W) && aligned16(W_hi);
-  dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, splits);
-  if (layout_a == 0 && layout_w == 0) launch_layout<0, 0>(g, vec, bf, grid, stream);
-  else if (layout_a == 0 && layout_w == 1) launch_layout<0, 1>(g, vec, bf, grid, stream);
-  else if (layout_a == 1 && layout_w == 0) launch_layout<1, 0>(g, vec, bf, grid, stream);
+  GemmArgs g{d.A, d.lda, d.W, d.ldw, d.W_hi, d.n_split, splits > 1 ? d.partials : d.C, d.ldc, d.M, d.N, d.K, d.bias1, d.bias2, d.rowbias,
+             d.ldrb, d.group > 0 ? d.group : 1, d.gate, d.ldg, d.a_relu, d.w_relu, d.act, d.accumulate, d.w_shift, d.w_group, k_chunk,
+             (long long)d.M * d.N};
+  const bool vec = (d.lda % 4 == 0) && (d.ldw % 4 == 0) && vs_aligned16(d.A) && vs_aligned16(d.W) && vs_aligned16(d.W_hi);
+  const bool bf = d.arith == VS_GEMM_FP32_BF16;
+  dim3 grid((d.N + BN - 1) / BN, (d.M + BM - 1) / BM, splits);
+  if (d.a_kmajor == 0 && d.w_kmajor == 0) launch_layout<0, 0>(g, vec, bf, grid, stream);
+  else if (d.a_kmajor == 0 && d.w_kmajor == 1) launch_layout<0, 1>(g, vec, bf, grid, stream);
+  else if (d.a_kmajor == 1 && d.w_kmajor == 0) launch_layout<1, 0>(g, vec, bf, grid, stream);
   else launch_layout<1, 1>(g, vec, bf, grid, stream);
   if (splits > 1) {
-    const long long n = (long long)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, partials, splits, n, C);
+    const long long n = (long long)d.M * d.N;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d.partials, splits, n, d.C);
   }
   VS_LAUNCH_CHECK();
   return 0;
 }
 
-int vs_gemm_general_impl(int layout_a, int layout_w, const float* A, int lda, const float* W, const float* W_hi,
-                         int n_split, int ldw, float* C, int ldc, int M, int N, int K,
-                         const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                         const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
-                         int w_shift, int w_group, int splits, float* partials, hipStream_t stream) {
-  return gemm_general(false, layout_a, layout_w, A, lda, W, W_hi, n_split, ldw, C, ldc, M, N, K, bias1, bias2, rowbias, ldrb, group,
-                      gate, ldg, a_relu, w_relu, act, accumulate, w_shift, w_group, splits, partials, stream);
+static bool on_split_kernel(const VsGemm& g) { return g.arith == VS_GEMM_SPLIT_F16 || g.arith == VS_GEMM_SPLIT_BF16; }
+
+int vs_gemm_check(const VsGemm& g) {
+  const bool split = on_split_kernel(g);
+  if (int rc = check_shared(g, split ? "gemm_f16x3" : "gemm")) return rc;
+  return split ? vs_gemm_f16x3_check(g) : check_fp32(g);
 }
 
-// The same contraction with both operands rounded to bf16 (VS_MATH_BF16: the head of the bf16 configuration)
-int vs_gemm_general_bf16_impl(int layout_a, int layout_w, const float* A, int lda, const float* W, const float* W_hi,
-                              int n_split, int ldw, float* C, int ldc, int M, int N, int K,
-                              const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                              const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
-                              int w_shift, int w_group, int splits, float* partials, hipStream_t stream) {
-  return gemm_general(true, layout_a, layout_w, A, lda, W, W_hi, n_split, ldw, C, ldc, M, N, K, bias1, bias2, rowbias, ldrb, group,
-                      gate, ldg, a_relu, w_relu, act, accumulate, w_shift, w_group, splits, partials, stream);
-}
-
-// C = act(opA(A) @ W^T + biases): both operands K-contiguous (the forward products).
-int vs_gemm_nt2_impl(const float* A, int lda, const float* W, const float* W_hi, int n_split, int ldw,
-                     float* C, int ldc, int M, int N, int K,
-                     const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                     int a_relu, int act, hipStream_t stream) {
-  return vs_gemm_general_impl(0, 0, A, lda, W, W_hi, n_split, ldw, C, ldc, M, N, K, bias1, bias2, rowbias, ldrb, group,
-                              nullptr, 0, a_relu, 0, act, 0, 0, 0, 1, nullptr, stream);
-}
-
-// vs_gemm_nt_impl with bf16-rounded operands (VS_MATH_BF16 head)
-int vs_gemm_nt_bf16_impl(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                         const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                         int a_relu, int act, hipStream_t stream) {
-  return vs_gemm_general_bf16_impl(0, 0, A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, K, bias1, bias2, rowbias, ldrb, group,
-                                   nullptr, 0, a_relu, 0, act, 0, 0, 0, 1, nullptr, stream);
-}
-
-int vs_gemm_nt_impl(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                    const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                    int a_relu, int act, hipStream_t stream) {
-  return vs_gemm_nt2_impl(A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, K, bias1, bias2, rowbias, ldrb, group,
-                          a_relu, act, stream);
+int vs_gemm_impl(const VsGemm& g, hipStream_t stream) {
+  if (int rc = vs_gemm_check(g)) return rc;
+  return on_split_kernel(g) ? vs_gemm_f16x3_launch(g, stream) : launch_fp32(g, stream);
 }

@@ -510,8 +510,8 @@ int vs_speaker_embed(const vs_speaker_dims* d, const void* prepared, size_t prep
   VS_CHECK_HIP(hipMemsetAsync(at<char>(ws, Wl.state), 0, Wl.state_bytes, stream));
   hipLaunchKernelGGL(spk_window_frames_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, utt_frames, utt_windows, U, N, s.S, s.W, total_frames, win_frame);
   // layer-0 input projection, once per frame: xproj[f][4H] = mel[:, f] @ W_ih0^T + b_ih0 + b_hh0 (fp32 matrix pipe; mel is K-major)
-  if (int rc = vs_gemm_general_impl(1, 0, mel, total_frames, at<float>(prepared, P.wih0), nullptr, 0x7fffffff, s.M, xproj, H4, total_frames, H4, s.M,
-                                    bias, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, 0, 0, 1, nullptr, stream)) return rc;
+  if (int rc = vs_gemm_impl({.A = mel, .lda = total_frames, .a_kmajor = 1, .W = at<float>(prepared, P.wih0), .ldw = s.M, .C = xproj, .ldc = H4,
+                             .M = total_frames, .N = H4, .K = s.M, .bias1 = bias}, stream)) return rc;
   StepArgs a;
   for (int l = 0; l < kMaxLayers; ++l) {
     a.wh[l] = l < s.L ? at<_Float16>(prepared, P.w[l]) : nullptr;
@@ -532,8 +532,8 @@ int vs_speaker_embed(const vs_speaker_dims* d, const void* prepared, size_t prep
   }
   VS_LAUNCH_CHECK();
   if (proj || dvec) {
-    if (int rc = vs_gemm_nt_impl(hl, s.H, at<float>(prepared, P.proj_w), s.H, pj, s.E, N, s.E, s.H, at<float>(prepared, P.proj_b), nullptr,
-                                 nullptr, 0, 1, 0, VS_ACT_NONE, stream)) return rc;
+    if (int rc = vs_gemm_impl({.A = hl, .lda = s.H, .W = at<float>(prepared, P.proj_w), .ldw = s.H, .C = pj, .ldc = s.E,
+                               .M = N, .N = s.E, .K = s.H, .bias1 = at<float>(prepared, P.proj_b)}, stream)) return rc;
   }
   if (dvec) {
     hipLaunchKernelGGL(spk_pool_kernel, dim3(U), dim3(256), 0, stream, pj, utt_windows, N, s.E, dvec);

@@ -241,10 +241,12 @@ int vs_stft_check_envelope(const VsStftShape& s) {
 
 int vs_stft_contract(bool split, int layout_w, const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
                      const float* a_scale2, const float* w_scale2, hipStream_t stream) {
-  if (split)
-    return vs_gemm_f16x3_impl(0, layout_w, A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, lda,
-                              nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, a_scale2, w_scale2, stream,
-                              VS_MATH_CODE_F16X3);
-  return vs_gemm_general_impl(0, layout_w, A, lda, W, nullptr, 0x7fffffff, ldw, C, ldc, M, N, K,
-                              nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, 0, 0, 1, nullptr, stream);
+  VsGemm g{.A = A, .lda = lda, .W = W, .ldw = ldw, .w_kmajor = layout_w, .C = C, .ldc = ldc, .M = M, .N = N, .K = K};
+  if (split) {
+    g.arith = VS_GEMM_SPLIT_F16;
+    g.K = lda;      // the split kernel contracts over the whole zero-padded rows
+    g.a_scale2 = a_scale2;
+    g.w_scale2 = w_scale2;
+  }
+  return vs_gemm_impl(g, stream);
 }

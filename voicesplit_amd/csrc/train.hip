@@ -276,8 +276,9 @@ int arm(const Step& st) {
 // the d-vector folded into a per-utterance row bias of the LSTM input projection (one direction)
 int dvec_bias(const Step& st, const float* dvec, int dir, hipStream_t s) {
   const vs_params* p = st.p;
-  return vs_gemm_nt_impl(dvec, st.d->E, p->w_ih[dir] + st.K8, st.KE, st.at<float>(st.L.dvbias) + (size_t)dir * 4 * st.H, 8 * st.H, st.B, 4 * st.H,
-                         st.d->E, p->b_ih[dir], p->b_hh[dir], nullptr, 0, 1, 0, VS_ACT_NONE, s);
+  return vs_gemm_impl({.A = dvec, .lda = st.d->E, .W = p->w_ih[dir] + st.K8, .ldw = st.KE,
+                       .C = st.at<float>(st.L.dvbias) + (size_t)dir * 4 * st.H, .ldc = 8 * st.H, .M = st.B, .N = 4 * st.H, .K = st.d->E,
+                       .bias1 = p->b_ih[dir], .bias2 = p->b_hh[dir]}, s);
 }
 
 // ---- the weight-only work of a bf16 step ------------------------------------------------------------------------------------------
@@ -465,9 +466,11 @@ int head(const Step& st, float* mask) {
   float* h1 = st.at<float>(st.L.fc1_out);
   // one launch, h1 in registers between the two contractions and stored once for the backward pass (head_fused.hip)
   if (st.head_fused) return vs_head_fused_impl(lstm_out, st.part, h1, nullptr, mask, st.M, 2 * H, FC1, FC2, st.stream);
-  const auto gemm_nt = st.nhwc ? vs_gemm_nt_bf16_impl : vs_gemm_nt_impl;
-  if (int rc = gemm_nt(lstm_out, 2 * H, p->fc1_w, 2 * H, h1, FC1, st.M, FC1, 2 * H, p->fc1_b, nullptr, nullptr, 0, 1, 1, VS_ACT_RELU, st.stream)) return rc;
-  return gemm_nt(h1, FC1, p->fc2_w, FC1, mask, FC2, st.M, FC2, FC1, p->fc2_b, nullptr, nullptr, 0, 1, 0, VS_ACT_SIGMOID, st.stream);
+  const VsGemmArith arith = st.nhwc ? VS_GEMM_FP32_BF16 : VS_GEMM_FP32;
+  if (int rc = vs_gemm_impl({.arith = arith, .A = lstm_out, .lda = 2 * H, .a_relu = 1, .W = p->fc1_w, .ldw = 2 * H, .C = h1, .ldc = FC1,
+                             .M = st.M, .N = FC1, .K = 2 * H, .bias1 = p->fc1_b, .act = VS_ACT_RELU}, st.stream)) return rc;
+  return vs_gemm_impl({.arith = arith, .A = h1, .lda = FC1, .W = p->fc2_w, .ldw = FC1, .C = mask, .ldc = FC2,
+                       .M = st.M, .N = FC2, .K = FC1, .bias1 = p->fc2_b, .act = VS_ACT_SIGMOID}, st.stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -493,7 +496,7 @@ int head_bwd(const Step& st, SideJoin& sj, const float* mask, const float* dmask
   float* tmp = st.at<float>(L.colsum_tmp);
   VsProfScope ps(VS_PROF_BWD_HEAD, stream);
   // VS_MATH_BF16: the four head contractions on bf16-rounded operands (fp32 accumulate, fp32 split-K partials)
-  const auto gemm = st.nhwc ? vs_gemm_general_bf16_impl : vs_gemm_general_impl;
+  const VsGemmArith arith = st.nhwc ? VS_GEMM_FP32_BF16 : VS_GEMM_FP32;
   // [r5] The two weight gradients of the head are leaves: with VS_OPT_HEAD_LEAF_SIDE they go to the side stream, where they run beside
   // the BPTT -- a latency-bound launch that leaves the CUs' arithmetic idle -- instead of in front of it (same kernels, same sums).
   const bool leaf_side = sj.side != nullptr && vs_opt(VS_OPT_HEAD_LEAF_SIDE) != 0;
@@ -513,30 +516,32 @@ int head_bwd(const Step& st, SideJoin& sj, const float* mask, const float* dmask
     if (int rc = vs_cvt_rows_bf16_impl(p->fc2_w, FC2, FC1, FC1, hb + o_w2, N1p, stream)) return rc;
     if (int rc = vs_cvt_rows_bf16_impl(p->fc1_w, FC1, 2 * H, 2 * H, hb + o_w1, N2p, stream)) return rc;
     if (int rc = vs_sigmoid_bwd_rows_impl(dmask, mask, dlogits, M, FC2, hb, K2p, stream)) return rc;
-    if (int rc = vs_gemm_bf16_impl(0, 1, hb, K2p, hb + o_w2, N1p, dfc1, FC1, nullptr, 0, M, FC1, FC2, nullptr, 0, 1, 0, stream, h1, FC1)) return rc;
+    if (int rc = vs_gemm_bf16_impl({.A = hb, .lda = K2p, .B = hb + o_w2, .ldb = N1p, .b_kmajor = 1, .C = dfc1, .ldc = FC1,
+                                    .M = M, .N = FC1, .K = FC2, .gate = h1, .ldg = FC1}, stream)) return rc;
   } else {
     if (int rc = vs_sigmoid_bwd_impl(dmask, mask, dlogits, (long long)M * FC2, stream)) return rc;
-    if (int rc = gemm(0, 1, dlogits, FC2, p->fc2_w, nullptr, 0x7fffffff, FC1, dfc1, FC1, M, FC1, FC2,
-                      nullptr, nullptr, nullptr, 0, 1, h1, FC1, 0, 0, VS_ACT_NONE, 0, 0, 0, 1, nullptr, stream)) return rc;
+    if (int rc = vs_gemm_impl({.arith = arith, .A = dlogits, .lda = FC2, .W = p->fc2_w, .ldw = FC1, .w_kmajor = 1, .C = dfc1, .ldc = FC1,
+                               .M = M, .N = FC1, .K = FC2, .gate = h1, .ldg = FC1}, stream)) return rc;
   }
   if (leaf_side) { if (int rc = sj.fork()) return rc; }
   if (int rc = vs_colsum_impl(dlogits, FC2, B, T, FC2, tmp_leaf, FC2, hs)) return rc;
   if (int rc = vs_colsum_impl(tmp_leaf, FC2, 1, B, FC2, g->fc2_b, FC2, hs)) return rc;
   // dW2 = dlogits^T @ h1
-  if (int rc = gemm(1, 1, dlogits, FC2, h1, nullptr, 0x7fffffff, FC1, g->fc2_w, FC1, FC2, FC1, M,
-                    nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, 0, 0, kSplitK, st.part, hs)) return rc;
+  if (int rc = vs_gemm_impl({.arith = arith, .A = dlogits, .lda = FC2, .a_kmajor = 1, .W = h1, .ldw = FC1, .w_kmajor = 1,
+                             .C = g->fc2_w, .ldc = FC1, .M = FC2, .N = FC1, .K = M, .splits = kSplitK, .partials = st.part}, hs)) return rc;
   if (int rc = vs_colsum_impl(dfc1, FC1, B, T, FC1, tmp_leaf, FC1, hs)) return rc;
   if (int rc = vs_colsum_impl(tmp_leaf, FC1, 1, B, FC1, g->fc1_b, FC1, hs)) return rc;
   // dW1 = dfc1^T @ relu(lstm_out)
-  if (int rc = gemm(1, 1, dfc1, FC1, lstm_out, nullptr, 0x7fffffff, 2 * H, g->fc1_w, 2 * H, FC1, 2 * H, M,
-                    nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 1, VS_ACT_NONE, 0, 0, 0, kSplitK, st.part, hs)) return rc;
+  if (int rc = vs_gemm_impl({.arith = arith, .A = dfc1, .lda = FC1, .a_kmajor = 1, .W = lstm_out, .ldw = 2 * H, .w_kmajor = 1, .w_relu = 1,
+                             .C = g->fc1_w, .ldc = 2 * H, .M = FC1, .N = 2 * H, .K = M, .splits = kSplitK, .partials = st.part}, hs)) return rc;
   // dlstm_out = (dfc1 @ W1) * (lstm_out > 0)
   if (head_bf16) {
     if (int rc = vs_cvt_rows_bf16_impl(dfc1, M, FC1, FC1, hb + o_df, K1p, stream)) return rc;
-    return vs_gemm_bf16_impl(0, 1, hb + o_df, K1p, hb + o_w1, N2p, dlstm, 2 * H, nullptr, 0, M, 2 * H, FC1, nullptr, 0, 1, 0, stream, lstm_out, 2 * H);
+    return vs_gemm_bf16_impl({.A = hb + o_df, .lda = K1p, .B = hb + o_w1, .ldb = N2p, .b_kmajor = 1, .C = dlstm, .ldc = 2 * H,
+                              .M = M, .N = 2 * H, .K = FC1, .gate = lstm_out, .ldg = 2 * H}, stream);
   }
-  return gemm(0, 1, dfc1, FC1, p->fc1_w, nullptr, 0x7fffffff, 2 * H, dlstm, 2 * H, M, 2 * H, FC1,
-              nullptr, nullptr, nullptr, 0, 1, lstm_out, 2 * H, 0, 0, VS_ACT_NONE, 0, 0, 0, 1, nullptr, stream);
+  return vs_gemm_impl({.arith = arith, .A = dfc1, .lda = FC1, .W = p->fc1_w, .ldw = 2 * H, .w_kmajor = 1, .C = dlstm, .ldc = 2 * H,
+                       .M = M, .N = 2 * H, .K = FC1, .gate = lstm_out, .ldg = 2 * H}, stream);
 }
 
 // BiLSTM: back-propagation through time; the gate gradients replace the gates in the tape
@@ -567,7 +572,8 @@ int lstm_leaves(const Step& st, const SideJoin& sj, const float* dvec, const vs_
   char* bfb = st.at<char>(L.lstm_bf16);
   // bf16 configuration: dW_ih[:, :8F] of both directions in one col x col contraction over K = B*T: rows < 4H -> dW_ih, the rest -> dW_ih_reverse
   auto dwih_bf16 = [&]() -> int {
-    return vs_gemm_bf16_impl(1, 1, bfb + st.lb.dxg, 8 * H, bfb + st.lb.feat, st.lb.Kp, g->w_ih[0], KE, g->w_ih[1], 4 * H, 8 * H, K8, M, nullptr, 0, 1, 0, ls);
+    return vs_gemm_bf16_impl({.A = bfb + st.lb.dxg, .lda = 8 * H, .a_kmajor = 1, .B = bfb + st.lb.feat, .ldb = st.lb.Kp, .b_kmajor = 1,
+                              .C = g->w_ih[0], .ldc = KE, .C2 = g->w_ih[1], .split_m = 4 * H, .M = 8 * H, .N = K8, .K = M}, ls);
   };
   // [r5] on a side stream it goes LAST: one persistent workgroup per CU, which slows the HBM-bound pass beside it down 3x
   const bool wih_last = sj.side != nullptr;
@@ -583,24 +589,24 @@ int lstm_leaves(const Step& st, const SideJoin& sj, const float* dvec, const vs_
     // dW_ih[:, :8F] = dxg_d^T @ feat
     if (st.nhwc) {
       if (dir == 0 && !wih_last) { if (int rc = dwih_bf16()) return rc; }
-    } else if (f16x3) {
-      if (int rc = vs_gemm_f16x3_impl(1, 1, dxg_d, 8 * H, feat, nullptr, 0x7fffffff, K8, g->w_ih[dir], KE, 4 * H, K8, M,
-                                      nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, gsc + 8, gsc, ls, st.d->math)) return rc;
     } else {
-      if (int rc = vs_gemm_general_impl(1, 1, dxg_d, 8 * H, feat, nullptr, 0x7fffffff, K8, g->w_ih[dir], KE, 4 * H, K8, M,
-                                        nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, 0, 0, 1, nullptr, ls)) return rc;
+      VsGemm dwih{.A = dxg_d, .lda = 8 * H, .a_kmajor = 1, .W = feat, .ldw = K8, .w_kmajor = 1, .C = g->w_ih[dir], .ldc = KE,
+                  .M = 4 * H, .N = K8, .K = M};
+      if (f16x3) { dwih.arith = VS_GEMM_SPLIT_F16; dwih.a_scale2 = gsc + 8; dwih.w_scale2 = gsc; }
+      if (int rc = vs_gemm_impl(dwih, ls)) return rc;
     }
     // dW_ih[:, 8F:] = (sum_t dxg_d)^T @ dvec    (the repeated d-vector columns, model.py:77-81)
-    if (int rc = vs_gemm_general_impl(1, 1, dsum + (size_t)dir * 4 * H, 8 * H, dvec, nullptr, 0x7fffffff, E, g->w_ih[dir] + K8, KE,
-                                      4 * H, E, B, nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0, 0, 0, 1, nullptr, ls)) return rc;
+    if (int rc = vs_gemm_impl({.A = dsum + (size_t)dir * 4 * H, .lda = 8 * H, .a_kmajor = 1, .W = dvec, .ldw = E, .w_kmajor = 1,
+                               .C = g->w_ih[dir] + K8, .ldc = KE, .M = 4 * H, .N = E, .K = B}, ls)) return rc;
     // dW_hh = sum_t dgates_t^T h_{t-1}: the lstm_out rows shifted by one frame inside each utterance
     // (VS_MATH_BF16: on bf16-rounded operands like the other contractions of this configuration)
-    if (int rc = (st.nhwc ? vs_gemm_general_bf16_impl : vs_gemm_general_impl)(1, 1, dxg_d, 8 * H, lstm_out + (size_t)dir * H, nullptr, 0x7fffffff, 2 * H,
-                                      g->w_hh[dir], H, 4 * H, H, M, nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, 0,
-                                      dir ? 1 : -1, T, kSplitK, st.part, ls)) return rc;
+    if (int rc = vs_gemm_impl({.arith = st.nhwc ? VS_GEMM_FP32_BF16 : VS_GEMM_FP32, .A = dxg_d, .lda = 8 * H, .a_kmajor = 1,
+                               .W = lstm_out + (size_t)dir * H, .ldw = 2 * H, .w_kmajor = 1, .C = g->w_hh[dir], .ldc = H,
+                               .M = 4 * H, .N = H, .K = M, .w_shift = dir ? 1 : -1, .w_group = T, .splits = kSplitK, .partials = st.part},
+                              ls)) return rc;
     if (g->dvec) {
-      if (int rc = vs_gemm_general_impl(0, 1, dsum + (size_t)dir * 4 * H, 8 * H, p->w_ih[dir] + K8, nullptr, 0x7fffffff, KE, g->dvec, E,
-                                        B, E, 4 * H, nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, dir, 0, 0, 1, nullptr, ls)) return rc;
+      if (int rc = vs_gemm_impl({.A = dsum + (size_t)dir * 4 * H, .lda = 8 * H, .W = p->w_ih[dir] + K8, .ldw = KE, .w_kmajor = 1,
+                                 .C = g->dvec, .ldc = E, .accumulate = dir, .M = B, .N = E, .K = 4 * H}, ls)) return rc;
     }
   }
   if (st.nhwc && wih_last) { if (int rc = dwih_bf16()) return rc; }
@@ -640,19 +646,16 @@ int dfeat_and_leaves(const Step& st, SideJoin& sj, const float* dvec, const vs_g
     VsProfScope ps(VS_PROF_BWD_LSTM_GEMM, stream);
     if (st.nhwc) {
       // dfeat = dxg @ [W_ih; W_ih_reverse][:, :8F]: both directions in one contraction over K = 8H
-      if (int rc = vs_gemm_bf16_impl(0, 1, bfb + st.lb.dxg, 8 * H, bfb + st.lb.wih, st.lb.Kp, dfeat, K8, nullptr, 0, M, K8, 8 * H,
-                                     nullptr, 0, 1, 0, stream)) return rc;
+      if (int rc = vs_gemm_bf16_impl({.A = bfb + st.lb.dxg, .lda = 8 * H, .B = bfb + st.lb.wih, .ldb = st.lb.Kp, .b_kmajor = 1,
+                                      .C = dfeat, .ldc = K8, .M = M, .N = K8, .K = 8 * H}, stream)) return rc;
     } else {
       for (int dir = 0; dir < 2; ++dir) {
         const float* dxg_d = dxg + (size_t)dir * 4 * H;
         // dfeat (+)= dxg_d @ W_ih[:, :8F]
-        if (f16x3) {
-          if (int rc = vs_gemm_f16x3_impl(0, 1, dxg_d, 8 * H, p->w_ih[dir], nullptr, 0x7fffffff, KE, dfeat, K8, M, K8, 4 * H,
-                                          nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, dir, gsc + 8, gsc + 2, stream, st.d->math)) return rc;
-        } else {
-          if (int rc = vs_gemm_general_impl(0, 1, dxg_d, 8 * H, p->w_ih[dir], nullptr, 0x7fffffff, KE, dfeat, K8, M, K8, 4 * H,
-                                            nullptr, nullptr, nullptr, 0, 1, nullptr, 0, 0, 0, VS_ACT_NONE, dir, 0, 0, 1, nullptr, stream)) return rc;
-        }
+        VsGemm df{.A = dxg_d, .lda = 8 * H, .W = p->w_ih[dir], .ldw = KE, .w_kmajor = 1, .C = dfeat, .ldc = K8, .accumulate = dir,
+                  .M = M, .N = K8, .K = 4 * H};
+        if (f16x3) { df.arith = VS_GEMM_SPLIT_F16; df.a_scale2 = gsc + 8; df.w_scale2 = gsc + 2; }
+        if (int rc = vs_gemm_impl(df, stream)) return rc;
       }
     }
   }

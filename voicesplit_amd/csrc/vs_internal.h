@@ -2,6 +2,7 @@
 // train.hip (training forward + backward orchestration) and capi.hip (the kernel-level surface), and
 // the small host helpers the orchestration files share.  Internal to libvoicesplit_hip.so.
 #pragma once
+#include <limits.h>
 #include "vs_common.h"
 
 // capi.hip: opt-in per-stage timing scope (see vs_profile_begin in the public header)
@@ -46,7 +47,6 @@ int vs_conv64_fwd_impl(const float* in, const float* wp, const float* scale, con
 int vs_pow2_scale_impl(const float* x, long long n, unsigned* amax_scratch, float* scale2, hipStream_t);
 int vs_scale_from_absmax_impl(const unsigned* amax, int n, float* scale2, hipStream_t);
 int vs_absmax_accum_impl(const float* x, long long n, unsigned* amax, hipStream_t);
-// gemm_f16x3.hip
 // gemm_f16x3.hip: operands split into f16 hi/lo arrays by a pass of their own
 size_t vs_gemm_presplit_bytes(int M, int N, int K);
 int vs_split_rows_impl(const float* x, int rows, int K, int ld, const float* scale2, _Float16* hi, _Float16* lo, int relu, hipStream_t,
@@ -55,11 +55,6 @@ int vs_gemm_presplit_impl(const _Float16* Ah, const _Float16* Al, const _Float16
                           float* C, int ldc, int M, int N, const float* bias1, const float* bias2,
                           const float* rowbias, int ldrb, int group, int act, int accumulate,
                           const float* a_scale2, const float* w_scale2, hipStream_t, int math = VS_MATH_CODE_F16X3);
-int vs_gemm_f16x3_impl(int layout_a, int layout_w, const float* A, int lda, const float* W, const float* W_hi,
-                       int n_split, int ldw, float* C, int ldc, int M, int N, int K,
-                       const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                       const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
-                       const float* a_scale2, const float* w_scale2, hipStream_t, int math = VS_MATH_CODE_F16X3);
 // The split-f16 operand arrays of the LSTM input GEMM inside one scratch region (256-byte aligned pieces): A = feat as hi / lo rows
 // [M][Kp], then W_ih of both directions as hi / lo rows [8H][Kp].  cnn8 of the whole-path eval forward writes A itself, the GEMM
 // reads it: both sides take their addresses from here.  (A prepared blob keeps its W halves in pieces of nw bytes each.)
@@ -231,31 +226,61 @@ int vs_conv_last_dgrad_impl(const float* dz, const float* w, float* din, int B, 
 int vs_conv_last_wgrad_impl(const float* dz, const float* in, float* part, float* dw, int B, int T, int F, hipStream_t);
 int vs_conv_first_wgrad_impl(const float* dz, const float* x, double* acc, float* dw, int B, int T, int F, hipStream_t);
 int vs_reduce_partials_impl(const float* part, int G, int n, float* out, hipStream_t);
-// gemm_mfma.hip
-int vs_gemm_general_impl(int layout_a, int layout_w, const float* A, int lda, const float* W, const float* W_hi,
-                         int n_split, int ldw, float* C, int ldc, int M, int N, int K,
-                         const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                         const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
-                         int w_shift, int w_group, int splits, float* partials, hipStream_t);
-int vs_gemm_general_bf16_impl(int layout_a, int layout_w, const float* A, int lda, const float* W, const float* W_hi,
-                         int n_split, int ldw, float* C, int ldc, int M, int N, int K,
-                         const float* bias1, const float* bias2, const float* rowbias, int ldrb, int group,
-                         const float* gate, int ldg, int a_relu, int w_relu, int act, int accumulate,
-                         int w_shift, int w_group, int splits, float* partials, hipStream_t);
-int vs_gemm_nt_impl(const float*, int, const float*, int, float*, int, int, int, int, const float*, const float*, const float*, int, int, int, int, hipStream_t);
+// gemm_mfma.hip, gemm_f16x3.hip: every dense contraction on fp32 operands, C[M][N] (+)= gate(act(opA(A) @ opW(W)^T + bias terms)), is
+// one VsGemm handed to vs_gemm_impl.  A call site names the fields that differ from the defaults, in declaration order.
+enum VsGemmArith {
+  VS_GEMM_FP32,         // gemm_mfma.hip: fp32 matrix instruction, bitwise an fp32 fmaf chain
+  VS_GEMM_FP32_BF16,    // gemm_mfma.hip: the same kernel with both operands rounded to bf16 while staged (the head of VS_MATH_BF16)
+  VS_GEMM_SPLIT_F16,    // gemm_f16x3.hip: operands split into f16 hi + lo, three products (needs a_scale2 / w_scale2)
+  VS_GEMM_SPLIT_BF16,   // gemm_f16x3.hip: that kernel's single-product bf16 instance (VS_MATH_BF16 without room for bf16 operand copies)
+};
+// which kernel and rounding a site uses -- not dims.math: the bf16 configuration runs several leaves on VS_GEMM_FP32
+struct VsGemm {
+  VsGemmArith arith = VS_GEMM_FP32;
+  // A: element (m, k) at m * lda + k, or K-major (a_kmajor) at k * lda + m; a_relu: read as max(A, 0)
+  const float* A = nullptr; int lda = 0; int a_kmajor = 0; int a_relu = 0;
+  // W: element (n, k) at n * ldw + k, or K-major at k * ldw + n.  W_hi: rows n >= n_split come from W_hi[n - n_split] (two matrices
+  // stacked along N, K-contiguous only); n_split = INT_MAX: no stacked W
+  const float* W = nullptr; int ldw = 0; int w_kmajor = 0; int w_relu = 0; const float* W_hi = nullptr; int n_split = INT_MAX;
+  float* C = nullptr; int ldc = 0; int accumulate = 0;
+  int M = 0, N = 0, K = 0;
+  // bias1[n] + bias2[n] + rowbias[m / group][n]
+  const float *bias1 = nullptr, *bias2 = nullptr, *rowbias = nullptr; int ldrb = 0; int group = 1;
+  const float* gate = nullptr; int ldg = 0;      // elements where gate[m][n] <= 0 are written as 0
+  int act = VS_ACT_NONE;
+  int w_shift = 0, w_group = 0;                  // K-major W rows shifted by w_shift inside groups of w_group rows (fp32 kernel only)
+  // splits > 1 (fp32 kernel only): split-K through partials ([splits][M][N] floats), summed in a fixed order into a dense C that
+  // takes no epilogue terms
+  int splits = 1; float* partials = nullptr;
+  const float *a_scale2 = nullptr, *w_scale2 = nullptr;      // split kernel: {s, 1/s} of the two operands (vs_pow2_scale_impl)
+};
+int vs_gemm_impl(const VsGemm&, hipStream_t);
+int vs_gemm_check(const VsGemm&);      // every refusal of vs_gemm_impl, without a launch
+// gemm_f16x3.hip: the split kernel's own refusals and its launch behind vs_gemm_impl
+int vs_gemm_f16x3_check(const VsGemm&);
+int vs_gemm_f16x3_launch(const VsGemm&, hipStream_t);
+inline bool vs_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // head_fused.hip: relu -> fc1 -> relu -> fc2 -> sigmoid in one launch (VS_MATH_BF16); h1 stays in registers between the two contractions
 bool vs_head_fused_supported(int K1, int FC1, int FC2);
 size_t vs_head_fused_packed_bytes(int K1, int FC1, int FC2);
 int vs_head_fused_pack_impl(const float* w1, const float* b1, const float* w2, const float* b2, int K1, int FC1, int FC2, void* packed, hipStream_t);
 int vs_head_fused_impl(const float* lstm_out, const void* packed, float* h1_out, float* logits, float* mask,
                        int M, int K1, int FC1, int FC2, hipStream_t);
-int vs_gemm_nt_bf16_impl(const float*, int, const float*, int, float*, int, int, int, int, const float*, const float*, const float*, int, int, int, int, hipStream_t);
-int vs_gemm_nt2_impl(const float*, int, const float*, const float*, int, int, float*, int, int, int, int, const float*, const float*, const float*, int, int, int, int, hipStream_t);
 // gemm_bf16.hip: the LSTM contractions of the bf16 configuration (LDS-DMA ring, row / K-major operand forms)
 int vs_cvt_rows_bf16_impl(const float* src, long long rows, int K, int ld, void* dst, int Kp, hipStream_t);
-int vs_gemm_bf16_impl(int a_kmajor, int b_kmajor, const void* A, int lda, const void* B, int ldb, float* C, int ldc, float* C2, int split_m,
-                      int M, int N, int K, const float* rowbias, int ldrb, int group, int accumulate, hipStream_t,
-                      const float* gate = nullptr, int ldg = 0);
+// C[M][N] (+)= opA(A) opB(B) + rowbias[m / group][n] on bf16 operands (16-byte aligned, ld a multiple of 8; row-form operands zero
+// padded to a multiple of 64 in k).  a_kmajor / b_kmajor: 0 = element (i, k) at i * ld + k, 1 = at k * ld + i.
+struct VsGemmBf16 {
+  const void* A = nullptr; int lda = 0; int a_kmajor = 0;
+  const void* B = nullptr; int ldb = 0; int b_kmajor = 0;
+  float* C = nullptr; int ldc = 0;
+  float* C2 = nullptr; int split_m = 0;          // rows >= split_m are written to C2 (two output matrices stacked along M)
+  int M = 0, N = 0, K = 0;
+  const float* rowbias = nullptr; int ldrb = 0; int group = 1;
+  int accumulate = 0;
+  const float* gate = nullptr; int ldg = 0;      // elements where gate[m][n] <= 0 are written as 0 (never with C2)
+};
+int vs_gemm_bf16_impl(const VsGemmBf16&, hipStream_t);
 // layout of the three bf16 operand arrays inside one scratch region (256-byte aligned pieces): feat [M][Kp], W_ih [8H][Kp], dxg [M][8H]
 struct VsLstmBf16Layout { size_t feat, wih, dxg, total; int Kp; };
 inline VsLstmBf16Layout vs_lstm_bf16_layout(long long M, int K, int H) {
