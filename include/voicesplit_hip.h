@@ -1228,6 +1228,50 @@ int vs_fir_rows(const float* samples, long long total, const long long* at, cons
                 int L, const float* h, int R, int H, int math, float* y, int* valid, float* scale, void* stream);
 int vs_row_energy(const float* y, int B, int L, double* energy, void* stream);
 
+/* =============================================================================================
+ * ABI 11 (additive entries).  The FFT form of the per-row FIR: uniformly partitioned overlap-save convolution in fp32 with kept filter
+ * spectra, for responses of up to 32768 taps.  tests/fir_fft_ref.py restates this text.
+ *
+ * Bk = VS_FIR_FFT_BLOCK = 2048, N = 2 Bk, Bk + 1 bins.  A response of nh taps is cut into P = ceil(nh / Bk) partitions,
+ *   H_p = rfft(h[p Bk .. (p + 1) Bk) zero-padded to N);  taps at k >= nh count as zero whatever the row holds.
+ * For row b, with x(p) = samples[p] for lo[b] <= p < at[b] + L and 0 elsewhere:
+ *   window q        w_q = x(at + (q - 1) Bk .. at + (q + 1) Bk)
+ *   output block j  i = j Bk .. (j + 1) Bk - 1:  y_j = the last Bk samples of irfft(sum_{p = 0 .. P - 1, ascending, from zero} rfft(w_{j-p}) H_p)
+ * which is vs_fir_rows' definition of y with nh = nh[hrow[b]], fixed when the spectra were made.  Nothing outside [lo[b], at[b] + L)
+ * is read.  Twiddle factors come from a table computed in fp64 and rounded once to fp32 (no fast-math sincos anywhere); every sum
+ * runs in one fixed order; no atomics.
+ *
+ * vs_fir_spectra_bytes(R, H): the size of the spectra blob of h [R][H], 1 <= H <= 32768; 0 and a message otherwise.
+ * vs_fir_spectra: builds the blob -- opaque, caller-owned: the twiddle table, the partition count of every response and the spectra.
+ *   The library keeps no lazily initialised state: everything a rows call needs beside its arguments is in the blob.  nh_host [R] in
+ *   HOST memory is checked before anything is launched (1 <= nh <= H, else -1 and a message); nh [R] is the same table on the device.
+ *   Two launches on the caller's stream.
+ * vs_fir_fft_workspace_bytes(B, L, H): the size of a rows call's workspace (the window spectra); 0 and a message when out of range.
+ * vs_fir_rows_fft: the convolution.  at, lo [B] int64 and hrow [B] int32 on the device; y [B][L]; any alignment of at.  Validity as in
+ *   vs_fir_rows: a row with lo < 0, lo > at, at + L > total or hrow outside 0 .. R - 1 is not read: valid[b] = -1 and a row of zeros;
+ *   otherwise valid[b] = 1.  Host-checkable argument errors (NULL, B outside 1 .. 65535, L outside 1 .. 2^24, H outside 1 .. 32768,
+ *   R < 1, total < L, a blob or workspace that is too small) return -1 and a message naming the value.  R and H are those the blob
+ *   was made with.  The workspace is scratch: what it held before changes nothing, and nothing in it outlives the call.  Two launches.
+ *
+ * What holds, and what tests/test_gpu_fir_fft.py holds it to:
+ *   The bits of a row depend only on the samples it reads and on its response: not on B, the row's index, hrow's value, where the
+ *   response sits in the table, R, at's alignment in the flat buffer, the call, or the bytes the workspace held before.
+ *   A row of zero samples gives exact zeros.
+ *   Error against the exact sum, per output of block j:  |y - y64| <= kappa 2^-24 log2(N) E_j,  E_j = sum_p ||w_{j-p}||_2 ||h_p||_2
+ *   (h_p: the taps of partition p).  THE BOUND IS GLOBAL TO A BLOCK: the error of a transform is spread over its 2048 outputs, so a
+ *   quiet output beside a loud one carries the block's error.  vs_fir_rows' bound is per output (a multiple of sum_k |h_k| |x_{n-k}|)
+ *   and does not allow that: where the quiet passages of a row matter more than its loud ones, use the direct form.
+ *   kappa = 8 kappa_ref, kappa_ref the same ratio of a float32 pocketfft restatement (scipy.fft) over the test's cases, computed
+ *   from the reference alone; the figures are in DESIGN.md 6.8m.
+ * ============================================================================================= */
+#define VS_FIR_FFT_BLOCK 2048
+size_t vs_fir_spectra_bytes(int R, int H);
+int vs_fir_spectra(const float* h, const int* nh_host, const int* nh, int R, int H, void* spectra, size_t spectra_bytes, void* stream);
+size_t vs_fir_fft_workspace_bytes(int B, int L, int H);
+int vs_fir_rows_fft(const float* samples, long long total, const long long* at, const long long* lo, const int* hrow, int B, int L,
+                    const void* spectra, size_t spectra_bytes, int R, int H, void* workspace, size_t workspace_bytes, float* y, int* valid,
+                    void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

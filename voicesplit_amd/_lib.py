@@ -291,6 +291,11 @@ SIGNATURES = {
     "vs_rir_shoebox": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "vs_fir_rows": (c_int, [_P, c_longlong, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "vs_row_energy": (c_int, [_P, c_int, c_int, _P, _P]),
+    # the FFT form of the per-row FIR with kept filter spectra
+    "vs_fir_spectra_bytes": (c_size_t, [c_int, c_int]),
+    "vs_fir_spectra": (c_int, [_P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
+    "vs_fir_fft_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vs_fir_rows_fft": (c_int, [_P, c_longlong, _P, _P, _P, c_int, c_int, _P, c_size_t, c_int, c_int, _P, c_size_t, _P, _P, _P]),
 }
 
 _lib = None

@@ -345,7 +345,9 @@ class MixtureBatches:
     ratio (``_reverberant``); with both None, the default, the path above is the one that runs.  history: "clip" = the reverberation
     of what the clip holds in front of the crop (from its trimmed start) rings into the crop, "zero" = silence in front of the crop.
     target: "reverberant" = the clean talker with the full response, "early" = with the response cut 50 ms behind the direct path
-    (the mixture keeps the full response).  math: the FIR's arithmetic, "f16x3" (matrix cores) or "fp32".
+    (the mixture keeps the full response).  math: the FIR's arithmetic, "f16x3" (matrix cores), "fp32", or "fft": the full-response
+    rows go through ``vs_fir_rows_fft`` with the pool's kept spectra (responses of up to 32768 taps; made once per pool), the
+    ``target="early"`` rows stay on the f16x3 direct form (about 900 taps, where the direct form wins).
     A drawn pool belongs to ONE epoch: when ``items`` / ``epoch`` is asked for another epoch than ``rir_pool.epoch``, ``self.rir_pool``
     is replaced by ``rir_pool.redraw(epoch)`` (the object that was passed in is left as it is) -- a host loop over the rooms and one
     ``vs_rir_shoebox`` call, tens of milliseconds for a few hundred responses, once per epoch.  This holds for epoch 0 too: a pool
@@ -360,8 +362,8 @@ class MixtureBatches:
             raise ValueError(f"history must be 'clip' or 'zero', got {history!r}")
         if target not in ("reverberant", "early"):
             raise ValueError(f"target must be 'reverberant' or 'early', got {target!r}")
-        if math not in ("f16x3", "fp32"):
-            raise ValueError(f"math must be 'f16x3' or 'fp32', got {math!r}")
+        if math not in ("f16x3", "fp32", "fft"):
+            raise ValueError(f"math must be 'f16x3', 'fp32' or 'fft', got {math!r}")
         if sir_db is not None:
             sir_db = (float(sir_db[0]), float(sir_db[1]))
             if not sir_db[0] <= sir_db[1]:
@@ -472,8 +474,16 @@ class MixtureBatches:
         if early:
             at2, lo2 = torch.cat((at2, at2[:B])), torch.cat((lo2, lo2[:B]))
             hrow, nh = torch.cat((hrow, hrow[:B])), torch.cat((nh, d["nh_early"][0]))
-        scratch, _, _ = reverb.fir_rows(self.pool.flat, at2.contiguous(), lo2.contiguous(), nh.contiguous(), hrow.contiguous(), pool.h, L,
-                                        self.math)
+        if self.math == "fft":
+            scratch = torch.empty(rows, L, dtype=torch.float32, device=dev)
+            reverb.fir_rows_fft(self.pool.flat, at2[:2 * B].contiguous(), lo2[:2 * B].contiguous(), hrow[:2 * B].contiguous(), pool.spectra, L,
+                                out=scratch[:2 * B])
+            if early:
+                reverb.fir_rows(self.pool.flat, at2[2 * B:].contiguous(), lo2[2 * B:].contiguous(), nh[2 * B:].contiguous(),
+                                hrow[2 * B:].contiguous(), pool.h_early, L, "f16x3", out=scratch[2 * B:])
+        else:
+            scratch, _, _ = reverb.fir_rows(self.pool.flat, at2.contiguous(), lo2.contiguous(), nh.contiguous(), hrow.contiguous(), pool.h, L,
+                                            self.math)
         if self.sir_db is not None:
             e = reverb.row_energy(scratch[:2 * B])
             ratio = e[:B] / e[B:] * torch.pow(10.0, -d["sir"][0] / 10.0)
@@ -981,18 +991,48 @@ def add_reverb_arguments(ap) -> None:
                     "reverberation times in seconds, uniform in LO .. HI")
     ap.add_argument("--sir-db", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="scale the interferer so that the "
                     "target-to-interferer energy ratio of every mixture is uniform in LO .. HI dB")
+    ap.add_argument("--reverb-csv", default=None, metavar="FILE", help="measured room responses instead of drawn rooms: one room per "
+                    "line, two columns [target_response,interferer_response] (wav files of up to 32768 samples at the configured "
+                    "rate; names relative to the CSV's directory); responses longer than 8192 taps need --reverb-math fft")
+    ap.add_argument("--reverb-math", choices=("f16x3", "fp32", "fft"), default=None, help="the FIR's arithmetic (default f16x3, the "
+                    "direct form on the matrix cores; fft: partitioned FFT convolution with kept spectra, responses of up to 32768 taps)")
 
 
 def reverb_arguments(args, sample_rate: int, device, seed: int) -> Optional[dict]:
     """The ``MixtureBatches`` arguments of --reverb-rooms / --rt60 / --sir-db; None without them (the path that runs is then the
     one without reverberation, line for line)."""
-    if not args.reverb_rooms and args.sir_db is None:
+    csv_path, math = getattr(args, "reverb_csv", None), getattr(args, "reverb_math", None)
+    if not args.reverb_rooms and args.sir_db is None and not csv_path:
         return None
     out = {"sir_db": None if args.sir_db is None else tuple(args.sir_db), "seed": seed}
+    if csv_path and args.reverb_rooms:
+        raise ValueError("--reverb-csv and --reverb-rooms both name the pool of responses: give one")
     if args.reverb_rooms:
         from .reverb import RirPool
         out["rir_pool"] = RirPool(args.reverb_rooms, device, seed=seed, rt60=tuple(args.rt60), fs=sample_rate)
+    if csv_path:
+        from .reverb import RirPool
+        out["rir_pool"] = RirPool.from_files(read_reverb_csv(csv_path), sample_rate, device)
+    if math is not None:
+        out["math"] = math
     return out
+
+
+def read_reverb_csv(path: str):
+    """The (target response, interferer response) file pairs of --reverb-csv; names are relative to the CSV's directory."""
+    root = os.path.dirname(os.path.abspath(path))
+    pairs = []
+    with open(path, newline="") as f:
+        for k, row in enumerate(csv.reader(f)):
+            row = [c.strip() for c in row if c.strip()]
+            if not row:
+                continue
+            if len(row) != 2:
+                raise ValueError(f"{path}:{k + 1}: expected two columns [target_response,interferer_response], got {len(row)}")
+            pairs.append(tuple(c if os.path.isabs(c) else os.path.join(root, c) for c in row))
+    if not pairs:
+        raise ValueError(f"{path}: no rooms")
+    return pairs
 
 
 def main(argv=None):
@@ -1020,8 +1060,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.no_overlay != bool(args.noise_csv):
         ap.error("--no-overlay and --noise-csv go together")
-    if args.no_overlay and (args.reverb_rooms or args.sir_db):
-        ap.error("--reverb-rooms and --sir-db serve the overlaid mixtures only, not --no-overlay")
+    if args.no_overlay and (args.reverb_rooms or args.sir_db or args.reverb_csv):
+        ap.error("--reverb-rooms, --reverb-csv and --sir-db serve the overlaid mixtures only, not --no-overlay")
     c = load_config(args.config)
     audio_cfg = resolve_audio(c.audio)
     form = c.dataset["format"] if "dataset" in c and "format" in c.dataset else None
